@@ -1,8 +1,20 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the 2048 rollout + PPO engine on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: launched by torch.distributed.run, one rank per GPU, backend nccl = RCCL)
+
+A plain run sets up, runs W warm-up and K timed steps and prints the headline line (`value`, `ms_per_step`, the phase split
+of the timed steps); everything else below ("Also on the JSON line") is measured only with --full.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy (float32 /
+float64, < 64 MB in all; the inputs are fixed by the seeds, so two builds can be compared file by file):
+  policy_parameters        every parameter of the policy after the last update, flattened in named_parameters() order
+  update_metrics           float64 [policy_loss, value_loss, entropy_loss, total_loss, kl_divergence, n_updates]
+  rollout_stats            float64 [mean_max_episode_reward, max_episode_reward, mean_episode_length, timesteps, episodes]
+  episode_lengths, episode_max_rewards   per episode of the last collect (this rank's boards)
+  rollout_rows             a fixed sample (seed 0) of row indices into the last collect's rollout buffer, and at those rows
+  rollout_boards [S, 16], rollout_actions, rollout_masks (legal-action bits), rollout_terms, rollout_rewards,
+  rollout_log_probs, rollout_values, rollout_advantages, rollout_returns (raw GAE, before normalisation)
 
 Workload (BASELINE.json configs[2] at N=1, configs[3] at N=8): 65 536 parallel boards PER GPU, the reference's
 default Transformer policy (3.96 M parameters) in bf16, random-init weights, boards generated on the device by
@@ -12,7 +24,8 @@ HIP compaction, then the clipped-surrogate update (5 epochs x up to 300 000 samp
 one flat gradient all-reduce per minibatch when N > 1) -- the reference's configs/trainer/default.yaml.
 `value` = live env-steps gathered by all ranks in the K timed steps / wall time (max over ranks).
 
-Also on the JSON line (measured AFTER the timed region; none of it is part of `value`):
+Also on the JSON line (hip_graph always, the rest with --full; measured AFTER the timed region except in_loop, which adds HIP
+events around the policy-step launches of the timed steps; none of it is part of `value`):
   hip_graph        whether the update really replayed its captured hipGraph (false = the slower eager fallback ran)
   frozen_policy    the same iteration with the learning rate at 0: does not depend on how far the policy has trained
   fixed_horizon    the throughput mode (per-lane auto-reset, fixed horizon, bootstrapped GAE): full PPO iterations
@@ -304,6 +317,41 @@ def cpu_baseline(boards: int, total_seconds: float = 18.0):
             "cpu_model": model, "logical_cpus": os.cpu_count(), "physical_cores": phys, "matrix": matrix}
 
 
+DUMP_ROWS = 1 << 18  # rollout-buffer rows in the --dump-outputs sample (~10 MB of columns + 16 MB of boards)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(trainer, metrics: dict, out_dir: str) -> dict:
+    """What the last timed step handed its caller, as .npy files under out_dir (see the module docstring); -> {name: bytes}."""
+    arrays = {}
+    arrays["policy_parameters"] = torch.cat([p.detach().float().reshape(-1) for p in trainer.agent.parameters()]).cpu().numpy()
+    arrays["update_metrics"] = np.array([metrics.get(k, np.nan) for k in ("policy_loss", "value_loss", "entropy_loss",
+                                                                          "total_loss", "kl_divergence", "n_updates")], np.float64)
+    st = trainer.last_rollout_stats
+    arrays["rollout_stats"] = np.array([st.get(k, np.nan) for k in ("mean_max_episode_reward", "max_episode_reward",
+                                                                     "mean_episode_length", "timesteps", "episodes")], np.float64)
+    n_ep = int(st.get("episodes", 0)) // trainer.world
+    arrays["episode_lengths"] = np.asarray(list(trainer.episode_lengths)[-n_ep:] if n_ep else [], np.float32)
+    arrays["episode_max_rewards"] = np.asarray(list(trainer.episode_rewards)[-n_ep:] if n_ep else [], np.float32)
+    data = trainer.rollout_buffer.device_data(trainer.device)
+    n = int(data["rewards"].shape[0])
+    rows = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_ROWS), replace=False))
+    idx = torch.from_numpy(rows).to(trainer.device)
+    arrays["rollout_rows"] = rows.astype(np.float64)
+    for name, key in (("boards", "boards"), ("actions", "actions"), ("masks", "masks"), ("terms", "terms"),
+                      ("rewards", "rewards"), ("log_probs", "log_probs"), ("values", "values"),
+                      ("advantages", "raw_advantages"), ("returns", "raw_returns")):
+        if key in data:
+            arrays[f"rollout_{name}"] = data[key].index_select(0, idx).float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {name: int(a.nbytes) for name, a in arrays.items()}
+
+
 def main():
     if os.environ.get("G2048_BENCH_STACKS"):  # debugging aid: dump every thread's stack to stderr every N seconds
         import faulthandler
@@ -321,8 +369,13 @@ def main():
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--horizon", type=int, default=128, help="rows per lane of the fixed_horizon extra")
     ap.add_argument("--roofline-boards", type=int, default=1 << 24)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave out the extra runs (roofline and encoder stay)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: in_loop, frozen_policy, fixed_horizon, roofline, policy_step, "
+                         "policy_encoder, env_only, drop_in_*, mlp4096, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -352,7 +405,8 @@ def main():
     from src.runs import BatchRunner
 
     timed = _TimedPolicyStep(nv)
-    nv.policy_step = timed
+    if args.full:  # HIP events around every policy-step launch of the timed steps: the in_loop object
+        nv.policy_step = timed
     global_boards = args.boards * world
 
     def make_trainer(workload, seed=0, optim=OPTIM_CFG, **kw):
@@ -473,11 +527,13 @@ def main():
                           "mean_live_boards_per_launch": round(live_per_launch, 1),
                           "algorithmic_bytes_per_env_step": POLICY_STEP_BYTES, "achieved_GBps": round(gbs, 1),
                           "frac_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 5)}
+    if args.dump_outputs and rank == 0:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dump_outputs(trainer, last_metrics, args.dump_outputs)}
     del trainer
     torch.cuda.empty_cache()
 
-    # ------------------------------------------------------------------ extras, after the timed region
-    if not args.no_extras and args.workload == "transformer65536":
+    # ------------------------------------------------------------------ extras (--full), after the timed region
+    if args.full and not args.no_extras and args.workload == "transformer65536":
         # (all ranks: these trainers run the same collectives as the headline)
         fr = make_trainer(args.workload, optim=dict(OPTIM_CFG, max_lr=0.0))
         n, s, m = run_iterations(fr, global_boards, 1, 1)
@@ -503,7 +559,7 @@ def main():
                                         "bootstrapped at the horizon), same update; 1 warm-up + 2 timed iterations"}
         del fx
         torch.cuda.empty_cache()
-    if rank == 0:
+    if rank == 0 and args.full:
         out["roofline"] = step_kernel_roofline(dev, args.roofline_boards)
         if not args.no_extras:
             out["policy_step"] = policy_step_saturated(dev)
@@ -565,6 +621,7 @@ def main():
                 del ml
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.boards)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

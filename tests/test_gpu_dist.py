@@ -177,8 +177,8 @@ def test_bench_two_rank_dryrun_reaches_the_json_line(dev, tmp_path, ranks):
     env = dict(os.environ, G2048_BENCH_DRYRUN="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", str(ranks), "--steps", "1", "--warmup", "0",
-           "--boards", "2048", "--train-batch", "512", "--epochs", "1", "--no-extras", "--no-cpu-baseline", "--roofline-boards",
-           "65536"]
+           "--boards", "2048", "--train-batch", "512", "--epochs", "1", "--full", "--no-extras", "--no-cpu-baseline",
+           "--roofline-boards", "65536"]
     p = subprocess.run(cmd, env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
