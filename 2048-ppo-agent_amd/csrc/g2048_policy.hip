@@ -39,6 +39,9 @@
 // parks K, V (bf16, 17 KB per board) and the CLS residual row in HBM.  k_encoder_tail batches the CLS tokens of 128
 // boards per workgroup (one board per lane) through the rest of layer L-1: Q projection, attention of that single query
 // over its board's 17 keys in-lane (K/V from HBM), out-proj, feed-forward.
+//
+// "mean" reduction (g2048_policy_encoder_mean): k_encoder_main<MEAN> runs every layer in full like <FULL>; its epilogue stages
+// the board tokens' final residual rows in LDS and averages the 16 rows of each board in a fixed order.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -301,7 +304,8 @@ __device__ __forceinline__ void layer_norm(const f32x16 r[8], bf16x8 out[16]) {
     for (int k = 0; k < 16; ++k) park_in_agpr(out[k]);
 }
 
-constexpr int MODE_FULL = 0, MODE_HEAD = 1;
+// MODE_MEAN: all layers full, like MODE_FULL, then the "mean" reduction (the 16 board tokens averaged) instead of the CLS rows
+constexpr int MODE_FULL = 0, MODE_HEAD = 1, MODE_MEAN = 2;
 // HBM workspace of the two-kernel form, per board: K and V of the last layer as [head][key][lane half][16] bf16 (the 16
 // values a lane half holds for one (token, head) are contiguous), then the CLS residual row (256 f32).
 constexpr int64_t KV_ELEMS = (int64_t)NH * SEQ * HD;  // per board, per K or V
@@ -322,6 +326,10 @@ struct LdsMain {
     float bq[D], bo[D], b1[FF], b2[D];
 };
 static_assert(sizeof(LdsMain) <= 160 * 1024, "LDS budget");
+// MODE_MEAN's epilogue stages the final residual rows of the board tokens over the weight area: [7 boards x 16 tokens][MEAN_LD]
+// f32, rows padded by 16 B so that consecutive tokens start 4 banks apart
+constexpr int MEAN_LD = D + 4;
+static_assert(NBOARD * 16 * MEAN_LD * 4 <= (int)sizeof(LdsMain::w), "mean-pool stage fits over the weight area");
 
 template <int MODE>
 __global__ void __launch_bounds__(THREADS, 1)
@@ -803,15 +811,45 @@ k_encoder_main(const uint8_t *__restrict__ boards, const float *__restrict__ tab
         return;
     }
 
-    // ---- CLS rows out
-    if (tok_valid && tc == 0) {
-        float *dst = features + (board0 + tb) * D;
-        for (int j = 0; j < 8; ++j)
-            for (int g = 0; g < 4; ++g) {
-                f32x4 v;
-                for (int q = 0; q < 4; ++q) v[q] = R[j][4 * g + q];
-                *reinterpret_cast<f32x4 *>(dst + 32 * j + 8 * g + 4 * h) = v;
-            }
+    if constexpr (MODE == MODE_MEAN) {
+        // ---- mean of the 16 board tokens (reference transformer_encoder.py:188-190, encoder_output[:, 1:, :].mean(dim=1)).
+        // The last layer's "next layer" prefetches are range-checked but may still land in LDS: drain them before the
+        // weight area is reused as the stage.
+        dma_wait_all();
+        __syncthreads();
+        // the lane index is recomputed (v_mbcnt), not read from registers kept live through the layers:
+        // what the epilogue needs per lane would otherwise be spilled around the layer loop
+        const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        const int t = 64 * w + ln, mtok = 32 * w + (ln & 31), mtb = mtok / SEQ, mtc = mtok - mtb * SEQ, mh = ln >> 5;
+        float *const stage = reinterpret_cast<float *>(lds);
+        if (mtb < NBOARD && board0 + mtb < B && mtc != 0) {  // CLS and pad tokens write nothing
+            float *dst = stage + (mtb * 16 + mtc - 1) * MEAN_LD;
+            for (int j = 0; j < 8; ++j)
+                for (int g = 0; g < 4; ++g) {
+                    f32x4 v;
+                    for (int q = 0; q < 4; ++q) v[q] = R[j][4 * g + q];
+                    *reinterpret_cast<f32x4 *>(dst + 32 * j + 8 * g + 4 * mh) = v;
+                }
+        }
+        __syncthreads();
+        // thread t owns feature t: 16 rows summed in ascending token order (deterministic), coalesced 1 KiB rows out
+        for (int b = 0; b < NBOARD && board0 + b < B; ++b) {
+            const float *src = stage + b * 16 * MEAN_LD + t;
+            float s = 0.f;
+            for (int k = 0; k < 16; ++k) s += src[k * MEAN_LD];
+            features[(board0 + b) * D + t] = s * 0.0625f;
+        }
+    } else {
+        // ---- CLS rows out
+        if (tok_valid && tc == 0) {
+            float *dst = features + (board0 + tb) * D;
+            for (int j = 0; j < 8; ++j)
+                for (int g = 0; g < 4; ++g) {
+                    f32x4 v;
+                    for (int q = 0; q < 4; ++q) v[q] = R[j][4 * g + q];
+                    *reinterpret_cast<f32x4 *>(dst + 32 * j + 8 * g + 4 * h) = v;
+                }
+        }
     }
 }
 
@@ -1015,6 +1053,25 @@ extern "C" int g2048_policy_encoder(const uint8_t *boards, const float *embed_ta
         hipLaunchKernelGGL(k_encoder_tail, dim3((unsigned)((B + NTOK - 1) / NTOK)), dim3(THREADS), sizeof(LdsTail),
                            (hipStream_t)stream, wb, params_f32, n_layers, features, B, ws_k, ws_v, ws_r);
     }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : -(1000 + (int)e);
+}
+
+extern "C" int g2048_policy_encoder_mean(const uint8_t *boards, const float *embed_table, const float *cls_token,
+                                         const void *weights_bf16, const float *params_f32, int n_layers, float *features,
+                                         int64_t B, void *stream) {
+    if (!boards || !embed_table || !cls_token || !weights_bf16 || !params_f32 || !features || n_layers < 1 || B <= 0)
+        return G2048_EINVAL;
+    if (((uintptr_t)weights_bf16 & 15) || ((uintptr_t)params_f32 & 15) || ((uintptr_t)embed_table & 15) ||
+        ((uintptr_t)cls_token & 15) || ((uintptr_t)features & 15))
+        return G2048_EINVAL;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_encoder_main<MODE_MEAN>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)sizeof(LdsMain)) != hipSuccess)
+        return -(1000 + (int)hipGetLastError());
+    const unsigned blocks = (unsigned)((B + NBOARD - 1) / NBOARD);
+    hipLaunchKernelGGL(k_encoder_main<MODE_MEAN>, dim3(blocks), dim3(THREADS), sizeof(LdsMain), (hipStream_t)stream, boards,
+                       embed_table, cls_token, reinterpret_cast<const __bf16 *>(weights_bf16), params_f32, n_layers, features, B,
+                       (__bf16 *)nullptr, (__bf16 *)nullptr, (float *)nullptr);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : -(1000 + (int)e);
 }

@@ -47,6 +47,7 @@ SIGNATURES = {
     "g2048_compact": [_vp] * 18 + [_i64, _i64, _vp],
     "g2048_policy_encoder_workspace_bytes": [_i64],
     "g2048_policy_encoder": [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp],
+    "g2048_policy_encoder_mean": [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp],
     "g2048_attn_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, C.c_float,
                        C.c_float, C.c_uint64, _vp, _vp],
     "g2048_attn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -334,6 +335,16 @@ def policy_encoder(boards, embed_table, cls_token, weights_bf16, params_f32, n_l
         _dev(cls_token, f32, 256, "cls_token"), _dev(weights_bf16, torch.bfloat16, n_layers * 786432, "weights_bf16"),
         _dev(params_f32, f32, n_layers * 3328, "params_f32"), n_layers, _dev(features, f32, 256 * B, "features"), B,
         None if workspace is None else workspace.data_ptr(), _stream()), "g2048_policy_encoder")
+
+
+def policy_encoder_mean(boards, embed_table, cls_token, weights_bf16, params_f32, n_layers: int, features):
+    """The "mean" reduction (mean of the 16 board tokens' outputs); same packed blobs as policy_encoder."""
+    B = boards.numel() // 16
+    _check(load().g2048_policy_encoder_mean(
+        _dev(boards, u8, 16 * B, "boards"), _dev(embed_table, f32, 16 * 31 * 256, "embed_table"),
+        _dev(cls_token, f32, 256, "cls_token"), _dev(weights_bf16, torch.bfloat16, n_layers * 786432, "weights_bf16"),
+        _dev(params_f32, f32, n_layers * 3328, "params_f32"), n_layers, _dev(features, f32, 256 * B, "features"), B,
+        _stream()), "g2048_policy_encoder_mean")
 
 
 def attn_fwd(q_ptr: int, k_ptr: int, v_ptr: int, o, lse, B: int, H: int, Sq: int, strides, scale: float, p_drop: float,

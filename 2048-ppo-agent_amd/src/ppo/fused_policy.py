@@ -1,9 +1,9 @@
 """Rollout-time policy forward through the fused MFMA encoder kernel (csrc/g2048_policy.hip).
 
-Usable when the agent is a PPOAgent of the reference's default shape (d_model 256, 8 heads, feed-forward 1024,
-"cls" reduction) on a HIP device and the rollout is asked to run in bf16.  The encoder (embedding -> 17-token
-Transformer -> CLS feature) is one kernel; the two 3-layer heads stay in PyTorch (bf16 autocast) on the [B, 256]
-features.  Same numerics class as torch.autocast(bf16): bf16 GEMM inputs, f32 accumulation/residual/statistics.
+Usable when the agent is a PPOAgent of the reference's default shape (d_model 256, 8 heads, feed-forward 1024) on a
+HIP device and the rollout is asked to run in bf16.  The encoder (embedding -> 17-token Transformer -> CLS feature, or
+for a "mean" agent the mean of the 16 board tokens) is one kernel; the two 3-layer heads stay in PyTorch (bf16 autocast)
+on the [B, 256] features.  Same numerics class as torch.autocast(bf16): bf16 GEMM inputs, f32 accumulation/residual/statistics.
 """
 from __future__ import annotations
 
@@ -14,10 +14,11 @@ import torch
 from ..g2048 import native as nv
 
 
-def supports(agent) -> bool:
+def _shape_ok(agent) -> bool:
+    """A PPOAgent of the kernel's shape on a HIP device (either reduction)."""
     from .ppo_agent import PPOAgent
 
-    if not isinstance(agent, PPOAgent) or agent.reduction != "cls":
+    if not isinstance(agent, PPOAgent):
         return False
     t = agent.transformer
     p = next(agent.parameters())
@@ -26,13 +27,25 @@ def supports(agent) -> bool:
             and all(abs(l.norm1.eps - 1e-5) < 1e-12 and abs(l.norm2.eps - 1e-5) < 1e-12 for l in t.encoder.layers))
 
 
+def supports(agent) -> bool:
+    """Agents with the "cls" reduction (g2048_policy_encoder)."""
+    return _shape_ok(agent) and agent.reduction == "cls"
+
+
+def supports_mean(agent) -> bool:
+    """Agents with the "mean" reduction, the reference PPOAgent's default (g2048_policy_encoder_mean)."""
+    return _shape_ok(agent) and agent.reduction == "mean"
+
+
 class FusedPolicy:
-    """Packs the agent's encoder weights for ``g2048_policy_encoder`` (re-pack with ``refresh()`` after an update)."""
+    """Packs the agent's encoder weights for ``g2048_policy_encoder`` / ``g2048_policy_encoder_mean`` (re-pack with
+    ``refresh()`` after an update)."""
 
     def __init__(self, agent):
-        if not supports(agent):
+        if not (supports(agent) or supports_mean(agent)):
             raise ValueError("agent shape not supported by the fused encoder kernel")
         self.agent = agent
+        self.mean = agent.reduction == "mean"
         self._key = None
         self.refresh()
 
@@ -130,10 +143,16 @@ class FusedPolicy:
 
     @torch.no_grad()
     def features(self, boards: torch.Tensor, split=None) -> torch.Tensor:
-        """boards u8 [B, 16] -> CLS features f32 [B, 256].  ``split``: force (True) / forbid (False) the two-kernel form."""
+        """boards u8 [B, 16] -> CLS (or, for a "mean" agent, board-token mean) features f32 [B, 256].  ``split``: force (True) /
+        forbid (False) the two-kernel form of a "cls" agent; a "mean" agent reads every token of the last layer and has none."""
         boards = boards.contiguous()
         B = boards.shape[0]
         out = torch.empty((B, 256), dtype=torch.float32, device=boards.device)
+        if self.mean:
+            if split:
+                raise ValueError("the mean reduction has no two-kernel form (split=True)")
+            nv.policy_encoder_mean(boards, self.table, self.cls, self.weights, self.params, self.n_layers, out)
+            return out
         if split is None:
             split = B >= self.SPLIT_MIN_BOARDS
         ws = self._workspace(B, boards.device) if split else None

@@ -24,7 +24,7 @@ class TorchActionFunction:
     Parameters mirror the reference: ``agent``, ``use_mask`` (apply the legal-action mask to the logits),
     ``sample_actions`` (categorical sample vs argmax), ``device`` (where the agent runs).  Extra:
     ``amp_dtype`` runs the rollout forward under autocast (the reference rolls out in fp32) -- for bfloat16 and a
-    PPOAgent of the reference's default shape the encoder then runs in the fused MFMA kernel unless
+    PPOAgent of the reference's default shape ("cls" or "mean" reduction) the encoder then runs in the fused MFMA kernel unless
     ``use_fused=False``; ``sync_every`` is how many lock-steps are enqueued between polls of the device-side
     live-env counter.
     Side effect as in the reference: ``agent`` is moved to ``device`` and put in eval mode.
@@ -45,7 +45,7 @@ class TorchActionFunction:
         if amp_dtype == torch.bfloat16 and use_fused is not False:
             from . import fused_policy
 
-            if fused_policy.supports(self.agent):
+            if fused_policy.supports(self.agent) or fused_policy.supports_mean(self.agent):
                 self._fused = fused_policy.FusedPolicy(self.agent)
         # a cheap policy (the MLP of BASELINE configs[1]: ~15 launches of microseconds per lock-step) is launch-bound in eager
         # mode: with a ``graph_cache`` (owned by the caller, it outlives this object) the forward over ALL boards of the batch is

@@ -185,6 +185,15 @@ int g2048_policy_encoder(const uint8_t *boards, const float *embed_table, const 
                          const void *weights_bf16, const float *params_f32, int n_layers, float *features,
                          int64_t B, void *workspace, void *stream);
 
+/* The same encoder with the "mean" reduction, PPOAgent's default (src/ppo/ppo_agent.py:26): features f32[B][256] =
+ * encoder_output[:, 1:, :].mean(dim=1), the mean over the 16 board tokens (src/ppo/transformer_encoder.py:188-190).
+ * Blob formats, parameter folding and alignments as g2048_policy_encoder.  One kernel carries every token through all
+ * n_layers (every token of the last layer is read, so there is no split form and no workspace); the 16 rows of a board are
+ * summed in ascending token order in f32 and scaled by 1/16, so two calls give bit-identical features. */
+int g2048_policy_encoder_mean(const uint8_t *boards, const float *embed_table, const float *cls_token,
+                              const void *weights_bf16, const float *params_f32, int n_layers, float *features,
+                              int64_t B, void *stream);
+
 /* ---- policy network (update): attention for 17-token sequences ------------------------------------- */
 
 /* softmax(q k^T * scale) v with attention dropout, head_dim 32, Sk = 17 keys, Sq = 17 queries (or 1: the CLS row

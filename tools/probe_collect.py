@@ -1,5 +1,9 @@
 """Kernel breakdown of the collect phase (policy-in-the-loop rollout of 65536 boards with the bf16 Transformer).
-usage: python tools/probe_collect.py [boards] [--fp32]   (--fp32: the reference's rollout precision, the PyTorch fp32 module forward)"""
+usage: python tools/probe_collect.py [boards] [--fp32] [--reduction {cls,mean}] [--unfused] [--no-profile]
+  --fp32: the reference's rollout precision, the PyTorch fp32 module forward
+  --reduction: the agent's reduction (default cls, bench.py's model); "mean" is the reference PPOAgent's default
+  --unfused: bf16 rollout without the fused encoder kernels (the layer kernels forward-only + library-GEMM heads)
+  --no-profile: the collect wall time only"""
 import os
 import sys
 import time
@@ -15,9 +19,15 @@ from src.runs import BatchRunner
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 65536
 FP32 = "--fp32" in sys.argv
+RED = sys.argv[sys.argv.index("--reduction") + 1] if "--reduction" in sys.argv else "cls"
+assert RED in ("cls", "mean"), RED
+if "--unfused" in sys.argv:
+    from src.ppo import fused_policy
+
+    fused_policy.supports = fused_policy.supports_mean = lambda agent: False
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
-agent = PPOAgent(**bench.MODEL_CFG)
+agent = PPOAgent(**dict(bench.MODEL_CFG, reduction=RED))
 tr = PPOTrainer(agent, BatchRunner(0, device=dev), RolloutBuffer(31, 16, 4), bench.OPTIM_CFG, max_steps=500000, device=dev,
                 rollout_amp=not FP32, log_dir="/tmp/lg", **bench.TRAINER_CFG)
 tr.collect_rollouts(B, 1)
@@ -26,7 +36,10 @@ torch.cuda.synchronize()
 t = time.time()
 tr.collect_rollouts(B, 1)
 torch.cuda.synchronize()
-print("collect wall s", round(time.time() - t, 3), tr.last_rollout_stats)
+print(f"reduction {RED} fused {tr.batch_runner.act_fn._fused is not None} collect wall s", round(time.time() - t, 3),
+      tr.last_rollout_stats)
+if "--no-profile" in sys.argv:
+    sys.exit(0)
 tr.rollout_buffer.reset()
 from torch.profiler import ProfilerActivity, profile
 
