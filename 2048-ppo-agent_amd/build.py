@@ -3,6 +3,7 @@
 hipcc cross-compiles without a GPU.  Every csrc/*.hip becomes an object under build/ (compiled in parallel, rebuilt only
 when it or a header changed), then one link.  The .so is git-ignored but travels with the working tree.
 """
+import glob
 import os
 import subprocess
 import sys
@@ -12,8 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["g2048.hip", "g2048_policy.hip", "g2048_attention.hip", "g2048_layernorm.hip", "g2048_ppo_loss.hip",
            "g2048_linear.hip", "g2048_optim.hip", "g2048_reduce.hip", "g2048_tail.hip", "g2048_dweight.hip", "g2048_rowgemm.hip", "g2048_mlp.hip"]
-HEADERS = [os.path.join(CSRC, "g2048_device.h"), os.path.join(CSRC, "g2048_colsum_final.h"), os.path.join(CSRC, "g2048_mfma.h"),
-           os.path.join(HERE, "..", "include", "g2048.h")]
+# every header under csrc/ plus the ABI: a new header cannot be forgotten by the staleness check
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "g2048.h")]
 OBJDIR = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "lib", "libg2048.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]

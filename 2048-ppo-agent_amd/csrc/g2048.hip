@@ -10,8 +10,10 @@
 
 #include "../../include/g2048.h"
 #include "g2048_device.h"
+#include "g2048_host.h"
 
 using namespace g2048;
+using namespace g2048_host;
 
 namespace {
 
@@ -366,10 +368,6 @@ __global__ void __launch_bounds__(kBlock) k_compact(const uint8_t *tr_boards, co
     }
 }
 
-inline int finish() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
-}
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 inline bool bad_mode(int m) { return m != G2048_RNG_LEGACY && m != G2048_RNG_PARTITIONABLE; }
 // global env indices and 2*j+1 must fit in 32 bits for the legacy split
@@ -388,7 +386,7 @@ int g2048_split(uint32_t key0, uint32_t key1, uint32_t *out_keys, int64_t n, int
     if (!out_keys || n <= 0 || n > kMaxEnvs || bad_mode(rng_mode)) return G2048_EINVAL;
     if (rng_mode) G2048_LAUNCH(k_split<1>, n, stream, key0, key1, out_keys, n);
     else G2048_LAUNCH(k_split<0>, n, stream, key0, key1, out_keys, n);
-    return finish();
+    return launch_status();
 }
 
 int g2048_chain_keys(uint32_t *key, uint32_t *subs, int64_t n, int rng_mode) {
@@ -413,32 +411,32 @@ int g2048_chain_keys(uint32_t *key, uint32_t *subs, int64_t n, int rng_mode) {
 int g2048_init(const uint32_t *keys, uint8_t *boards, uint8_t *masks, uint8_t *done, int64_t B, int rng_mode,
                void *stream) {
     if (!keys || !boards || !masks || !done || B <= 0 || B > kMaxEnvs || bad_mode(rng_mode)) return G2048_EINVAL;
-    if (((uintptr_t)boards & 15) || ((uintptr_t)keys & 7)) return G2048_EINVAL;
+    if (!aligned16(boards) || ((uintptr_t)keys & 7)) return G2048_EINVAL;
     if (rng_mode) G2048_LAUNCH(k_init<1>, B, stream, keys, boards, masks, done, B);
     else G2048_LAUNCH(k_init<0>, B, stream, keys, boards, masks, done, B);
-    return finish();
+    return launch_status();
 }
 
 int g2048_step(uint8_t *boards, uint8_t *masks, uint8_t *done, const int32_t *actions, const uint32_t *keys,
                float *rewards, int64_t B, int rng_mode, void *stream) {
     if (!boards || !masks || !done || !actions || !keys || !rewards || B <= 0 || B > kMaxEnvs || bad_mode(rng_mode))
         return G2048_EINVAL;
-    if (((uintptr_t)boards & 15) || ((uintptr_t)keys & 7)) return G2048_EINVAL;
+    if (!aligned16(boards) || ((uintptr_t)keys & 7)) return G2048_EINVAL;
     if (rng_mode) G2048_LAUNCH(k_step<1>, B, stream, boards, masks, done, actions, keys, rewards, B);
     else G2048_LAUNCH(k_step<0>, B, stream, boards, masks, done, actions, keys, rewards, B);
-    return finish();
+    return launch_status();
 }
 
 int g2048_observe(const uint8_t *boards, uint8_t *obs, int64_t B, void *stream) {
     if (!boards || !obs || B <= 0 || B > kMaxEnvs || ((uintptr_t)obs & 3)) return G2048_EINVAL;
     G2048_LAUNCH(k_observe, B * 124, stream, boards, obs, B);
-    return finish();
+    return launch_status();
 }
 
 int g2048_act_drul(const uint8_t *masks, int32_t *actions, int64_t B, void *stream) {
     if (!masks || !actions || B <= 0 || B > kMaxEnvs) return G2048_EINVAL;
     G2048_LAUNCH(k_act_drul, B, stream, masks, actions, B);
-    return finish();
+    return launch_status();
 }
 
 int g2048_act_random(const uint32_t *keys, const uint8_t *masks, int32_t *actions, float *log_probs, int64_t B,
@@ -447,31 +445,31 @@ int g2048_act_random(const uint32_t *keys, const uint8_t *masks, int32_t *action
     if ((uintptr_t)keys & 7) return G2048_EINVAL;
     if (rng_mode) G2048_LAUNCH(k_act_random<1>, B, stream, keys, masks, actions, log_probs, B);
     else G2048_LAUNCH(k_act_random<0>, B, stream, keys, masks, actions, log_probs, B);
-    return finish();
+    return launch_status();
 }
 
 int g2048_act_logits(const uint32_t *keys, const float *logits, const uint8_t *masks, int use_mask, int sample,
                      int32_t *actions, float *log_probs, int64_t B, int rng_mode, void *stream) {
     if (!keys || !logits || !masks || !actions || !log_probs || B <= 0 || B > kMaxEnvs || bad_mode(rng_mode))
         return G2048_EINVAL;
-    if (((uintptr_t)keys & 7) || ((uintptr_t)logits & 15)) return G2048_EINVAL;
+    if (((uintptr_t)keys & 7) || !aligned16(logits)) return G2048_EINVAL;
     if (rng_mode)
         G2048_LAUNCH(k_act_logits<1>, B, stream, keys, logits, masks, use_mask, sample, actions, log_probs, B);
     else
         G2048_LAUNCH(k_act_logits<0>, B, stream, keys, logits, masks, use_mask, sample, actions, log_probs, B);
-    return finish();
+    return launch_status();
 }
 
 int g2048_reset_fused(uint32_t sub0, uint32_t sub1, uint8_t *boards, uint8_t *masks, uint8_t *done,
                       int32_t *ep_len, int64_t B, int64_t B_total, int64_t env0, int rng_mode, void *stream) {
     if (!boards || !masks || !done || !ep_len || B <= 0 || env0 < 0 || B_total > kMaxEnvs || env0 + B > B_total ||
-        bad_mode(rng_mode) || ((uintptr_t)boards & 15))
+        bad_mode(rng_mode) || !aligned16(boards))
         return G2048_EINVAL;
     if (rng_mode)
         G2048_LAUNCH(k_reset_fused<1>, B, stream, sub0, sub1, boards, masks, done, ep_len, B, (u32)B_total, (u32)env0);
     else
         G2048_LAUNCH(k_reset_fused<0>, B, stream, sub0, sub1, boards, masks, done, ep_len, B, (u32)B_total, (u32)env0);
-    return finish();
+    return launch_status();
 }
 
 int g2048_rollout_fused(const uint32_t *step_subs, int n_steps, int64_t t0, uint8_t *boards, uint8_t *masks,
@@ -483,7 +481,7 @@ int g2048_rollout_fused(const uint32_t *step_subs, int n_steps, int64_t t0, uint
         B_total > kMaxEnvs || env0 + B > B_total || bad_mode(rng_mode) ||
         (policy != G2048_POLICY_DRUL && policy != G2048_POLICY_RANDOM))
         return G2048_EINVAL;
-    if (((uintptr_t)boards & 15) || ((uintptr_t)tr_boards & 15)) return G2048_EINVAL;
+    if (!aligned16(boards) || !aligned16(tr_boards)) return G2048_EINVAL;
     StepKeyTable tab;
     for (int s = 0; s < n_steps; ++s)
         for (int q = 0; q < 4; ++q) tab.k[s][q] = step_subs[4 * s + q];
@@ -499,7 +497,7 @@ int g2048_rollout_fused(const uint32_t *step_subs, int n_steps, int64_t t0, uint
         else G2048_RF(0, G2048_POLICY_DRUL);
     }
 #undef G2048_RF
-    return finish();
+    return launch_status();
 }
 
 static int policy_step_impl(int autoreset, uint32_t act_sub0, uint32_t act_sub1, uint32_t step_sub0, uint32_t step_sub1,
@@ -511,7 +509,7 @@ static int policy_step_impl(int autoreset, uint32_t act_sub0, uint32_t act_sub1,
         !tr_values || B <= 0 || env0 < 0 || B_total > kMaxEnvs || env0 + B > B_total || bad_mode(rng_mode))
         return G2048_EINVAL;
     if (!autoreset && !done) return G2048_EINVAL;  // (live_count may be NULL: no poll after this lock-step)
-    if (((uintptr_t)boards & 15) || ((uintptr_t)tr_boards & 15) || ((uintptr_t)logits & 15)) return G2048_EINVAL;
+    if (!aligned16(boards) || !aligned16(tr_boards) || !aligned16(logits)) return G2048_EINVAL;
     const u32 bt = (u32)B_total, e0 = (u32)env0;
 #define G2048_PS(M, A)                                                                                                   \
     G2048_LAUNCH((k_policy_step<M, A>), B, stream, act_sub0, act_sub1, step_sub0, step_sub1, logits, values, use_mask,  \
@@ -525,7 +523,7 @@ static int policy_step_impl(int autoreset, uint32_t act_sub0, uint32_t act_sub1,
         else G2048_PS(0, 0);
     }
 #undef G2048_PS
-    return finish();
+    return launch_status();
 }
 
 int g2048_policy_step(uint32_t act_sub0, uint32_t act_sub1, uint32_t step_sub0, uint32_t step_sub1,
@@ -560,7 +558,7 @@ int g2048_gae_tb(const float *tr_rewards, const float *tr_values, const int32_t 
     if (!tr_rewards || !tr_values || !ep_len || !tr_adv || !tr_ret || T <= 0 || B <= 0) return G2048_EINVAL;
     G2048_LAUNCH(k_gae_tb, B, stream, tr_rewards, tr_values, ep_len, tr_adv, tr_ret, T, B, (float)gamma,
                  (float)(gamma * lam));
-    return finish();
+    return launch_status();
 }
 
 int g2048_gae_tb_boot(const float *tr_rewards, const float *tr_values, const uint8_t *tr_meta, const float *last_values,
@@ -568,14 +566,14 @@ int g2048_gae_tb_boot(const float *tr_rewards, const float *tr_values, const uin
     if (!tr_rewards || !tr_values || !tr_meta || !last_values || !tr_adv || !tr_ret || T <= 0 || B <= 0) return G2048_EINVAL;
     G2048_LAUNCH(k_gae_tb_boot, B, stream, tr_rewards, tr_values, tr_meta, last_values, tr_adv, tr_ret, T, B, (float)gamma,
                  (float)(gamma * lam));
-    return finish();
+    return launch_status();
 }
 
 int g2048_gae_flat(const float *rewards, const float *values, const uint8_t *terms, float *adv, float *ret,
                    int64_t N, double gamma, double lam, void *stream) {
     if (!rewards || !values || !terms || !adv || !ret || N <= 0) return G2048_EINVAL;
     G2048_LAUNCH(k_gae_flat, N, stream, rewards, values, terms, adv, ret, N, (float)gamma, (float)(gamma * lam));
-    return finish();
+    return launch_status();
 }
 
 int g2048_compact(const uint8_t *tr_boards, const uint8_t *tr_meta, const float *tr_rewards, const float *tr_logp,
@@ -587,11 +585,11 @@ int g2048_compact(const uint8_t *tr_boards, const uint8_t *tr_meta, const float 
         !out_rewards || !out_terms || T <= 0 || B <= 0)
         return G2048_EINVAL;
     if ((out_logp && !tr_logp) || (out_values && !tr_values) || (out_adv && !tr_adv) || (out_ret && !tr_ret)) return G2048_EINVAL;
-    if (((uintptr_t)tr_boards & 15) || ((uintptr_t)out_boards & 15)) return G2048_EINVAL;
+    if (!aligned16(tr_boards) || !aligned16(out_boards)) return G2048_EINVAL;
     G2048_LAUNCH(k_compact, B * 64, stream, tr_boards, tr_meta, tr_rewards, tr_logp, tr_values, tr_adv, tr_ret, ep_len,
                  offsets, out_boards, out_actions, out_masks, out_rewards, out_logp, out_values, out_adv, out_ret, out_terms,
                  T, B);
-    return finish();
+    return launch_status();
 }
 
 }  // extern "C"

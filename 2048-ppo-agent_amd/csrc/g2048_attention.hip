@@ -15,8 +15,13 @@
 #include <stdlib.h>
 
 #include "../../include/g2048.h"
+#include "g2048_host.h"
+#include "g2048_mfma.h"
 
 namespace {
+
+using namespace g2048_mfma;
+using namespace g2048_host;
 
 constexpr int HD = 32, SK = 17, PAIRS = 3;  // (sample, head) pairs per wavefront when Sq = 17
 constexpr int ROW = HD + 4;                  // f32 row stride in LDS (pad: pairs land on different banks)
@@ -31,14 +36,6 @@ struct Params {
     uint32_t seed0, seed1, thr;
     const uint64_t *seed_state;  // optional device-resident word mixed into the seed (advanced between hipGraph replays)
 };
-
-__device__ __forceinline__ float bf2f(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f) {
-    const __bf16 b = (__bf16)f;
-    return *reinterpret_cast<const uint16_t *>(&b);
-}
-
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) { return (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16); }
 
 // 32 bf16 (64 B) -> 32 f32
 __device__ __forceinline__ void load_row(const uint16_t *p, float out[HD]) {
@@ -56,16 +53,8 @@ __device__ __forceinline__ void store_row(uint16_t *p, const float in[HD]) {
     uint4 *p4 = reinterpret_cast<uint4 *>(p);
     for (int c = 0; c < 4; ++c) {
         uint32_t w[4];
-        for (int e = 0; e < 4; ++e) w[e] = (uint32_t)f2bf(in[8 * c + 2 * e]) | ((uint32_t)f2bf(in[8 * c + 2 * e + 1]) << 16);
+        for (int e = 0; e < 4; ++e) w[e] = pack2(in[8 * c + 2 * e], in[8 * c + 2 * e + 1]);
         p4[c] = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-}
-
-__device__ __forceinline__ void mix_seed_state(Params &P) {
-    if (P.seed_state) {
-        const uint64_t s = *P.seed_state;
-        P.seed0 ^= (uint32_t)s * 0x9E3779B1u;
-        P.seed1 += (uint32_t)(s >> 32) * 0x85EBCA77u + (uint32_t)s;
     }
 }
 
@@ -82,20 +71,17 @@ __device__ __forceinline__ int64_t xcd_block() {
 
 // dropout keep decision for probability element `idx`: a 32-bit mix of (seed, idx), deterministic across fwd/bwd
 __device__ __forceinline__ bool keep_mask(const Params &P, uint64_t idx) {
-    uint32_t x = (uint32_t)idx * 0x9E3779B1u ^ P.seed0;
-    x ^= (uint32_t)(idx >> 32) * 0x85EBCA77u + P.seed1;
-    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-    return (x >> 8) >= P.thr;
+    return keep_elem(P.seed0, P.seed1, P.thr, idx);
 }
-// The same decision for element base + c when the caller has m = (uint32_t)base * 0x9E3779B1 at hand: (base + c) * C = base * C + c * C
+// The same decision for element base + c when the caller has m = (uint32_t)base * HASH_MUL at hand: (base + c) * C = base * C + c * C
 // (mod 2^32), so a run of elements costs one add of a compile-time constant each instead of a 64-bit add and two of the four
 // quarter-rate v_mul_lo_u32.  SMALL (host-checked: every element index of the launch is below 2^32): the high word adds nothing
 // but seed1.  Otherwise the plain form.
 template <bool SMALL>
 __device__ __forceinline__ bool keep_rel(const Params &P, uint64_t base, uint32_t m, uint32_t c) {
     if constexpr (!SMALL) return keep_mask(P, base + c);
-    uint32_t x = (m + c * 0x9E3779B1u) ^ (P.seed0 ^ P.seed1);
-    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
+    uint32_t x = (m + c * HASH_MUL) ^ (P.seed0 ^ P.seed1);
+    G2048_HASH_FIN(x);
     return (x >> 8) >= P.thr;
 }
 
@@ -121,7 +107,7 @@ __device__ __forceinline__ void put_row(float *row, const float v[HD]) {
 
 // ------------------------------------------------------------------------------------------------ Sq = 17
 __global__ void __launch_bounds__(64) k_attn_fwd17(Params P, uint16_t *__restrict__ o, float *__restrict__ lse) {
-    mix_seed_state(P);
+    mix_seed_state(P.seed_state, P.seed0, P.seed1);
     __shared__ float Ks[PAIRS * PSTRIDE], Vs[PAIRS * PSTRIDE];
     const int lane = threadIdx.x, pl = lane / SK, i = lane - pl * SK;
     const int64_t pair = xcd_block() * PAIRS + pl;
@@ -167,7 +153,7 @@ __global__ void __launch_bounds__(64) k_attn_fwd17(Params P, uint16_t *__restric
 __global__ void __launch_bounds__(64) k_attn_bwd17(Params P, const uint16_t *__restrict__ dout, const float *__restrict__ lse,
                                                    uint16_t *__restrict__ dq, uint16_t *__restrict__ dk,
                                                    uint16_t *__restrict__ dv) {
-    mix_seed_state(P);
+    mix_seed_state(P.seed_state, P.seed0, P.seed1);
     // K/V tiles serve the first phase (dS, dQ), then the same LDS holds Q/dO for the second (dK, dV): 22 KB per
     // workgroup instead of 37, i.e. 7 resident waves per CU instead of 4
     __shared__ float Ks[PAIRS * PSTRIDE], Vs[PAIRS * PSTRIDE];
@@ -231,7 +217,7 @@ __global__ void __launch_bounds__(64) k_attn_bwd17(Params P, const uint16_t *__r
 
 // ------------------------------------------------------------------------------------------------ Sq = 1 (CLS row)
 __global__ void __launch_bounds__(64) k_attn_fwd1(Params P, uint16_t *__restrict__ o, float *__restrict__ lse) {
-    mix_seed_state(P);
+    mix_seed_state(P.seed_state, P.seed0, P.seed1);
     const int64_t pair = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (pair >= P.B * P.H) return;
     const int64_t b = pair / P.H;
@@ -265,7 +251,7 @@ __global__ void __launch_bounds__(64) k_attn_fwd1(Params P, uint16_t *__restrict
 __global__ void __launch_bounds__(64) k_attn_bwd1(Params P, const uint16_t *__restrict__ dout, const float *__restrict__ lse,
                                                   uint16_t *__restrict__ dq, uint16_t *__restrict__ dk,
                                                   uint16_t *__restrict__ dv) {
-    mix_seed_state(P);
+    mix_seed_state(P.seed_state, P.seed0, P.seed1);
     const int64_t pair = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (pair >= P.B * P.H) return;
     const int64_t b = pair / P.H;
@@ -318,7 +304,7 @@ __device__ __forceinline__ void unpack8(const uint4 u, float f[8]) {
     }
 }
 __device__ __forceinline__ uint4 pack8(const float f[8]) {
-    return make_uint4(pack_bf16(f[0], f[1]), pack_bf16(f[2], f[3]), pack_bf16(f[4], f[5]), pack_bf16(f[6], f[7]));
+    return make_uint4(pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7]));
 }
 __device__ __forceinline__ float quad_dot(const float a[8], const uint4 u) {
     float f[8], s = 0.f;
@@ -329,7 +315,7 @@ __device__ __forceinline__ float quad_dot(const float a[8], const uint4 u) {
 }
 
 __global__ void __launch_bounds__(256) k_attn_fwd1_rows(Params P, uint16_t *__restrict__ o, float *__restrict__ lse) {
-    mix_seed_state(P);
+    mix_seed_state(P.seed_state, P.seed0, P.seed1);
     const int l = threadIdx.x & 31, h = l >> 2, c = l & 3;
     const int64_t b = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
     if (b >= P.B) return;  // (a whole 32-lane group)
@@ -369,7 +355,7 @@ __global__ void __launch_bounds__(256) k_attn_fwd1_rows(Params P, uint16_t *__re
 __global__ void __launch_bounds__(256) k_attn_bwd1_rows(Params P, const uint16_t *__restrict__ dout, const float *__restrict__ lse,
                                                         uint16_t *__restrict__ dq, uint16_t *__restrict__ dk,
                                                         uint16_t *__restrict__ dv) {
-    mix_seed_state(P);
+    mix_seed_state(P.seed_state, P.seed0, P.seed1);
     const int l = threadIdx.x & 31, h = l >> 2, c = l & 3;
     const int64_t b = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
     if (b >= P.B) return;
@@ -424,10 +410,6 @@ __global__ void __launch_bounds__(256) k_attn_bwd1_rows(Params P, const uint16_t
 //                                 after one v_permlane32_swap -> 16-byte stores
 // Dropout uses the element index of the scalar kernels ((pair * 17 + q) * 32 + key), so forward and backward of either
 // implementation can be mixed.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ int key_of(int i, int hf) { return (i & 3) + 8 * (i >> 2) + 4 * hf; }
 // LDS hand-over inside ONE wavefront (these kernels run 64-thread workgroups): the LDS unit executes a wave's DS instructions in
 // order, so all that is needed is that earlier DS traffic has been issued and returned before the dependent reads - not the
 // vmcnt(0) + s_barrier of __syncthreads(), which would also drain the global prefetch of the next head
@@ -436,7 +418,7 @@ __device__ __forceinline__ float xhalf(float x) { return __shfl_xor(x, 32); }
 
 template <bool SMALL>
 __global__ void __launch_bounds__(64) k_attn_fwd17_mfma(Params P, uint16_t *__restrict__ o, float *__restrict__ lse) {
-    mix_seed_state(P);
+    mix_seed_state(P.seed_state, P.seed0, P.seed1);
     __shared__ __attribute__((aligned(16))) uint16_t Vs[SK * HD];  // V of the current head, [17][32] bf16
     const int lane = threadIdx.x, r = lane & 31, hf = lane >> 5;
     // grid = B * splits: a wavefront owns heads [h0, h1) of one sample (splits = 2 doubles the waves in flight per CU)
@@ -447,7 +429,7 @@ __global__ void __launch_bounds__(64) k_attn_fwd17_mfma(Params P, uint16_t *__re
     const int rr = row_ok ? r : 0;
     const float c_log2 = P.scale * 1.4426950408889634f;
     const bool no_drop = !(P.p_drop > 0.f);
-    const uint32_t lane_km = (uint32_t)(r * 32 + 4 * hf) * 0x9E3779B1u;  // the lane's share of keep_rel's m
+    const uint32_t lane_km = (uint32_t)(r * 32 + 4 * hf) * HASH_MUL;  // the lane's share of keep_rel's m
     const uint16_t *kb = P.k + b * P.k_sb + rr * P.k_ss + 8 * hf, *qb = P.q + b * P.q_sb + rr * P.q_ss + 8 * hf;
     const uint16_t *vb = P.v + b * P.v_sb + (lane >> 2) * P.v_ss + 8 * (lane & 3);  // rows 0..15: one 16-byte chunk per lane
     const uint16_t *v16 = P.v + b * P.v_sb + 16 * P.v_ss + 8 * (lane & 3);          // row 16: lanes 0..3
@@ -497,18 +479,18 @@ __global__ void __launch_bounds__(64) k_attn_fwd17_mfma(Params P, uint16_t *__re
         l += p[8];
         l += xhalf(l);
         const float inv = P.inv_keep / l;
-        const uint64_t base = ((uint64_t)pair * SK + r) * 32 + 4 * hf;  // key_of(i, hf) = (i & 3) + 8 (i >> 2) + 4 hf
-        const uint32_t km = (uint32_t)(pair * (SK * 32)) * 0x9E3779B1u + lane_km;
+        const uint64_t base = ((uint64_t)pair * SK + r) * 32 + 4 * hf;  // rowof(i, hf) = (i & 3) + 8 (i >> 2) + 4 hf
+        const uint32_t km = (uint32_t)(pair * (SK * 32)) * HASH_MUL + lane_km;
         _Pragma("unroll") for (int i = 0; i < 9; ++i) {
-            const bool keep = no_drop | keep_rel<SMALL>(P, base, km, (i & 3) + 8 * (i >> 2));  // (bitwise: no branch per element)
+            const bool keep = no_drop | keep_rel<SMALL>(P, base, km, rowof(i, 0));  // (bitwise: no branch per element)
             p[i] = keep ? p[i] * inv : 0.f;
         }
-        const uint4 pb0 = make_uint4(pack_bf16(p[0], p[1]), pack_bf16(p[2], p[3]), pack_bf16(p[4], p[5]), pack_bf16(p[6], p[7]));
-        const uint4 pb1 = make_uint4(pack_bf16(p[8], 0.f), 0u, 0u, 0u);
+        const uint4 pb0 = make_uint4(pack2(p[0], p[1]), pack2(p[2], p[3]), pack2(p[4], p[5]), pack2(p[6], p[7]));
+        const uint4 pb1 = make_uint4(pack2(p[8], 0.f), 0u, 0u, 0u);
         // ---- V^T in the accumulator's key order: lane = feature d
         uint32_t w[4];
         _Pragma("unroll") for (int j = 0; j < 8; j += 2)
-            w[j >> 1] = (uint32_t)Vs[key_of(j, hf) * HD + r] | ((uint32_t)Vs[key_of(j + 1, hf) * HD + r] << 16);
+            w[j >> 1] = (uint32_t)Vs[rowof(j, hf) * HD + r] | ((uint32_t)Vs[rowof(j + 1, hf) * HD + r] << 16);
         const uint4 va0 = make_uint4(w[0], w[1], w[2], w[3]);
         const uint4 va1 = make_uint4(hf == 0 ? (uint32_t)Vs[16 * HD + r] : 0u, 0u, 0u, 0u);
         // ---- O^T = V^T P^T
@@ -516,11 +498,11 @@ __global__ void __launch_bounds__(64) k_attn_fwd17_mfma(Params P, uint16_t *__re
         _Pragma("unroll") for (int i = 0; i < 16; ++i) ot[i] = 0.f;
         ot = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, va0), __builtin_bit_cast(bf16x8, pb0), ot, 0, 0, 0);
         ot = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, va1), __builtin_bit_cast(bf16x8, pb1), ot, 0, 0, 0);
-        // ---- lane (q, hf) holds d = key_of(i, hf): swap halves so that every lane owns 8 consecutive d, store
+        // ---- lane (q, hf) holds d = rowof(i, hf): swap halves so that every lane owns 8 consecutive d, store
         uint16_t *orow = o + ((b * SK + rr) * P.H + h) * HD + 8 * hf;
         _Pragma("unroll") for (int mm = 0; mm < 2; ++mm) {
-            uint32_t ax = pack_bf16(ot[8 * mm + 0], ot[8 * mm + 1]), ay = pack_bf16(ot[8 * mm + 2], ot[8 * mm + 3]);
-            uint32_t bx = pack_bf16(ot[8 * mm + 4], ot[8 * mm + 5]), by = pack_bf16(ot[8 * mm + 6], ot[8 * mm + 7]);
+            uint32_t ax = pack2(ot[8 * mm + 0], ot[8 * mm + 1]), ay = pack2(ot[8 * mm + 2], ot[8 * mm + 3]);
+            uint32_t bx = pack2(ot[8 * mm + 4], ot[8 * mm + 5]), by = pack2(ot[8 * mm + 6], ot[8 * mm + 7]);
             const auto sx = __builtin_amdgcn_permlane32_swap(ax, bx, false, false);
             const auto sy = __builtin_amdgcn_permlane32_swap(ay, by, false, false);
             if (row_ok) *reinterpret_cast<uint4 *>(orow + 16 * mm) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
@@ -547,7 +529,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5)))
 k_attn_bwd17_mfma(Params P, const uint16_t *__restrict__ dout, const float *__restrict__ lse,
                                                         uint16_t *__restrict__ dq, uint16_t *__restrict__ dk,
                                                         uint16_t *__restrict__ dv) {
-    mix_seed_state(P);
+    mix_seed_state(P.seed_state, P.seed0, P.seed1);
     __shared__ __attribute__((aligned(16))) uint16_t Ks[SK * HD], Qs[SK * HD], Gs[SK * HD];
     __shared__ float lseS[32], delS[32];
     const int lane = threadIdx.x, r = lane & 31, hf = lane >> 5;
@@ -564,7 +546,7 @@ k_attn_bwd17_mfma(Params P, const uint16_t *__restrict__ dout, const float *__re
     auto zpad = [&](uint4 u) { return make_uint4(u.x & live, u.y & live, u.z & live, u.w & live); };
     const bool no_drop = !(P.p_drop > 0.f);
     // the lane's share of keep_rel's m: lane = query (elements (pair * 17 + r) * 32 + key) and lane = key (... + query) * 32 + r)
-    const uint32_t lane_km1 = (uint32_t)(r * 32 + 4 * hf) * 0x9E3779B1u, lane_km2 = (uint32_t)(r + 128 * hf) * 0x9E3779B1u;
+    const uint32_t lane_km1 = (uint32_t)(r * 32 + 4 * hf) * HASH_MUL, lane_km2 = (uint32_t)(r + 128 * hf) * HASH_MUL;
     auto fetch = [&](int h) -> Op {
         Op x;
         const uint16_t *kp = kb + h * HD, *qp = qb + h * HD, *vp = vb + h * HD, *gp = gb + h * HD;
@@ -583,23 +565,23 @@ k_attn_bwd17_mfma(Params P, const uint16_t *__restrict__ dout, const float *__re
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a0), __builtin_bit_cast(bf16x8, b0), acc, 0, 0, 0);
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a1), __builtin_bit_cast(bf16x8, b1), acc, 0, 0, 0);
     };
-    // registers 0..7 of a lane are rows key_of(i, hf) < 16, register 8 of half 0 is row 16; all others are padding
+    // registers 0..7 of a lane are rows rowof(i, hf) < 16, register 8 of half 0 is row 16; all others are padding
     auto gather = [&](const uint16_t *tile) -> Frag {  // tile^T in register order: lane = feature d
         uint32_t w[4];
-        _Pragma("unroll") for (int j = 0; j < 8; j += 2) w[j >> 1] = (uint32_t)tile[key_of(j, hf) * HD + r] | ((uint32_t)tile[key_of(j + 1, hf) * HD + r] << 16);
+        _Pragma("unroll") for (int j = 0; j < 8; j += 2) w[j >> 1] = (uint32_t)tile[rowof(j, hf) * HD + r] | ((uint32_t)tile[rowof(j + 1, hf) * HD + r] << 16);
         return Frag{make_uint4(w[0], w[1], w[2], w[3]), make_uint4(hf == 0 ? (uint32_t)tile[16 * HD + r] : 0u, 0u, 0u, 0u)};
     };
-    auto store_rows = [&](const f32x16 &t, uint16_t *row) {  // lane (row r, hf) of a transposed result: d = key_of(i, hf)
+    auto store_rows = [&](const f32x16 &t, uint16_t *row) {  // lane (row r, hf) of a transposed result: d = rowof(i, hf)
         _Pragma("unroll") for (int mm = 0; mm < 2; ++mm) {
-            uint32_t ax = pack_bf16(t[8 * mm + 0], t[8 * mm + 1]), ay = pack_bf16(t[8 * mm + 2], t[8 * mm + 3]);
-            uint32_t bx = pack_bf16(t[8 * mm + 4], t[8 * mm + 5]), by = pack_bf16(t[8 * mm + 6], t[8 * mm + 7]);
+            uint32_t ax = pack2(t[8 * mm + 0], t[8 * mm + 1]), ay = pack2(t[8 * mm + 2], t[8 * mm + 3]);
+            uint32_t bx = pack2(t[8 * mm + 4], t[8 * mm + 5]), by = pack2(t[8 * mm + 6], t[8 * mm + 7]);
             const auto sx = __builtin_amdgcn_permlane32_swap(ax, bx, false, false);
             const auto sy = __builtin_amdgcn_permlane32_swap(ay, by, false, false);
             if (row_ok) *reinterpret_cast<uint4 *>(row + 16 * mm) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
         }
     };
-#define G2048_AS_OPERAND(x) Frag{make_uint4(pack_bf16(x[0], x[1]), pack_bf16(x[2], x[3]), pack_bf16(x[4], x[5]), pack_bf16(x[6], x[7])), \
-                                 make_uint4(pack_bf16(x[8], 0.f), 0u, 0u, 0u)}
+#define G2048_AS_OPERAND(x) Frag{make_uint4(pack2(x[0], x[1]), pack2(x[2], x[3]), pack2(x[4], x[5]), pack2(x[6], x[7])), \
+                                 make_uint4(pack2(x[8], 0.f), 0u, 0u, 0u)}
     {
         Op c = fetch(h);
         c.k0 = zpad(c.k0); c.k1 = zpad(c.k1); c.q0 = zpad(c.q0); c.q1 = zpad(c.q1);
@@ -617,11 +599,11 @@ k_attn_bwd17_mfma(Params P, const uint16_t *__restrict__ dout, const float *__re
         float ds[9], delta = 0.f;
         {
             const uint64_t base = ((uint64_t)pair * SK + r) * 32 + 4 * hf;
-            const uint32_t km = (uint32_t)(pair * (SK * 32)) * 0x9E3779B1u + lane_km1;
+            const uint32_t km = (uint32_t)(pair * (SK * 32)) * HASH_MUL + lane_km1;
             float p[9], dp[9];
             _Pragma("unroll") for (int i = 0; i < 9; ++i) {
                 const bool valid = i < 8 || hf == 0;
-                const bool keep = no_drop | keep_rel<SMALL>(P, base, km, (i & 3) + 8 * (i >> 2));
+                const bool keep = no_drop | keep_rel<SMALL>(P, base, km, rowof(i, 0));
                 p[i] = valid ? exp2f(st[i] * c_log2 - lq2) : 0.f;
                 dp[i] = (valid && keep) ? dpt[i] * P.inv_keep : 0.f;
                 delta = fmaf(p[i], dp[i], delta);
@@ -633,15 +615,15 @@ k_attn_bwd17_mfma(Params P, const uint16_t *__restrict__ dout, const float *__re
         wave_lds_sync();  // K/Q/dO tiles, lse and delta are in LDS
         const Frag dsb = G2048_AS_OPERAND(ds), kt = gather(Ks);
         store_rows(mfma2(kt.a, kt.b, dsb.a, dsb.b), dq + b * P.q_sb + rr * P.q_ss + h * HD + 8 * hf);
-        // ---- orientation 2: lane = key, register i = query key_of(i, hf)
+        // ---- orientation 2: lane = key, register i = query rowof(i, hf)
         const f32x16 s2 = mfma2(c.q0, c.q1, c.k0, c.k1), dp2 = mfma2(c.g0, c.g1, c.v0, c.v1);
         float ds2[9], pd2[9];
-        const uint64_t base2 = (uint64_t)pair * (SK * 32) + r + 128 * hf;  // query key_of(i, hf): 32 x ((i & 3) + 8 (i >> 2)) more
-        const uint32_t km2 = (uint32_t)(pair * (SK * 32)) * 0x9E3779B1u + lane_km2;
+        const uint64_t base2 = (uint64_t)pair * (SK * 32) + r + 128 * hf;  // query rowof(i, hf): 32 x ((i & 3) + 8 (i >> 2)) more
+        const uint32_t km2 = (uint32_t)(pair * (SK * 32)) * HASH_MUL + lane_km2;
         _Pragma("unroll") for (int i = 0; i < 9; ++i) {
             const bool valid = i < 8 || hf == 0;
-            const int qi = valid ? key_of(i, hf) : 0;
-            const bool keep = no_drop | keep_rel<SMALL>(P, base2, km2, 32 * ((i & 3) + 8 * (i >> 2)));
+            const int qi = valid ? rowof(i, hf) : 0;
+            const bool keep = no_drop | keep_rel<SMALL>(P, base2, km2, 32 * rowof(i, 0));
             const float p = valid ? exp2f(s2[i] * c_log2 - lseS[qi] * 1.4426950408889634f) : 0.f;
             const float dp = (valid && keep) ? dp2[i] * P.inv_keep : 0.f;
             ds2[i] = p * (dp - delS[qi]) * P.scale;
@@ -659,7 +641,7 @@ inline bool fill(Params &P, const void *q, const void *k, const void *v, int64_t
                  uint64_t seed, const uint64_t *seed_state) {
     if (!q || !k || !v || B <= 0 || H <= 0 || (Sq != 1 && Sq != SK) || !(p_drop >= 0.f && p_drop < 1.f)) return false;
     // rows are read/written as 4 x 16 bytes
-    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return false;
+    if (!aligned16(q, k, v)) return false;
     if ((q_sb | q_ss | k_sb | k_ss | v_sb | v_ss) & 7) return false;
     P.q = (const uint16_t *)q; P.k = (const uint16_t *)k; P.v = (const uint16_t *)v;
     P.B = B; P.H = H;
@@ -668,10 +650,6 @@ inline bool fill(Params &P, const void *q, const void *k, const void *v, int64_t
     P.seed0 = (uint32_t)seed; P.seed1 = (uint32_t)(seed >> 32); P.seed_state = seed_state;
     P.thr = (uint32_t)(p_drop * 16777216.0f);
     return true;
-}
-inline int done() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
 }
 // G2048_ATTN_SCALAR=1 keeps the scalar kernels (17-token: one lane per query row; CLS row: one lane per pair) (read per call: no
 // latch, no library state)
@@ -692,7 +670,7 @@ extern "C" int g2048_attn_fwd(const void *q, const void *k, const void *v, void 
                               int64_t q_sb, int64_t q_ss, int64_t k_sb, int64_t k_ss, int64_t v_sb, int64_t v_ss,
                               float scale, float p_drop, uint64_t seed, const uint64_t *seed_state, void *stream) {
     Params P;
-    if (!o || !lse || ((uintptr_t)o & 15) || !fill(P, q, k, v, B, H, Sq, q_sb, q_ss, k_sb, k_ss, v_sb, v_ss, scale, p_drop, seed, seed_state))
+    if (!o || !lse || !aligned16(o) || !fill(P, q, k, v, B, H, Sq, q_sb, q_ss, k_sb, k_ss, v_sb, v_ss, scale, p_drop, seed, seed_state))
         return G2048_EINVAL;
     const int64_t pairs = B * H;
     if (Sq == SK && use_mfma17())
@@ -708,7 +686,7 @@ extern "C" int g2048_attn_fwd(const void *q, const void *k, const void *v, void 
     else
         hipLaunchKernelGGL(k_attn_fwd1, dim3((unsigned)((pairs + 63) / 64)), dim3(64), 0, (hipStream_t)stream, P,
                            (uint16_t *)o, lse);
-    return done();
+    return launch_status();
 }
 
 extern "C" int g2048_attn_bwd(const void *q, const void *k, const void *v, const void *dout, const float *lse, void *dq,
@@ -716,7 +694,7 @@ extern "C" int g2048_attn_bwd(const void *q, const void *k, const void *v, const
                               int64_t k_ss, int64_t v_sb, int64_t v_ss, float scale, float p_drop, uint64_t seed,
                               const uint64_t *seed_state, void *stream) {
     Params P;
-    if (!dout || !lse || !dq || !dk || !dv || (((uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 15) ||
+    if (!dout || !lse || !dq || !dk || !dv || !aligned16(dout, dq, dk, dv) ||
         !fill(P, q, k, v, B, H, Sq, q_sb, q_ss, k_sb, k_ss, v_sb, v_ss, scale, p_drop, seed, seed_state))
         return G2048_EINVAL;
     const int64_t pairs = B * H;
@@ -732,5 +710,5 @@ extern "C" int g2048_attn_bwd(const void *q, const void *k, const void *v, const
     else
         hipLaunchKernelGGL(k_attn_bwd1, dim3((unsigned)((pairs + 63) / 64)), dim3(64), 0, (hipStream_t)stream, P,
                            (const uint16_t *)dout, lse, (uint16_t *)dq, (uint16_t *)dk, (uint16_t *)dv);
-    return done();
+    return launch_status();
 }

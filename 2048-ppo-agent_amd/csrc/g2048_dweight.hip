@@ -15,28 +15,20 @@
 #include <stdint.h>
 
 #include "../../include/g2048.h"
+#include "g2048_host.h"
+#include "g2048_mfma.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using namespace g2048_mfma;
+using namespace g2048_host;
+
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int TOKS = 64, BK = 128;
 
-__device__ __forceinline__ int rowof(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-
-// one LDS-DMA wave-instruction, 16 bytes per lane (lane l lands at lds + 16 l), scalar row base + per-lane byte offset.  Inline assembly
-// on purpose: for the builtin the compiler makes every later LDS read wait for the DMA (see g2048_linear.hip); the waits are explicit.
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void dma16(const void *sbase, uint32_t voff, uint32_t lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_addr) : "memory", "m0");
-}
-#pragma clang diagnostic pop
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
+// (dma16 and lds_barrier_asm come from g2048_mfma.h; the waits for the LDS-DMA are explicit, see there)
 __device__ __forceinline__ bf16x8 tr_pair(const char *p0, const char *p1) {
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)p0);
     const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)p1);
@@ -126,7 +118,7 @@ __device__ __forceinline__ void dweight_block(const __bf16 *__restrict__ dy, int
         if (DIST >= 3 && younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PER) : "memory");
         else if (younger >= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        lds_barrier();  // ... for every wave; and every wave is done with stage s - 1, whose buffer stage s + DIST takes
+        lds_barrier_asm();  // ... for every wave; and every wave is done with stage s - 1, whose buffer stage s + DIST takes
         const bool more = s + DIST < n_stages;
         const char *A = smem + (s % NBUF) * STAGE, *B = A + ABYTES;
         // every transposed read of the stage first, then the MFMAs as their operands arrive, with the fetch instructions of stage
@@ -170,7 +162,7 @@ __device__ __forceinline__ void dweight_block(const __bf16 *__restrict__ dy, int
         }
     }
     // ---- epilogue: the block as bf16 through LDS (rows of 256 bytes), then full rows to parts[slice][n0 ..][k0 ..]
-    lds_barrier();
+    lds_barrier_asm();
     if (parts_f32) {  // (uniform) f32 partials: the A/B switch of round 4 (G2048_DWEIGHT_PARTS=f32x8); [BN][128] f32 <= the stage buffers
         float *const sm = reinterpret_cast<float *>(smem);
 #pragma unroll
@@ -179,7 +171,7 @@ __device__ __forceinline__ void dweight_block(const __bf16 *__restrict__ dy, int
             for (int b = 0; b < KTW; ++b)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) sm[(32 * (NTW * wn + a) + rowof(i, h)) * BK + 32 * (KTW * wk + b) + r] = acc[a][b][i];
-        lds_barrier();
+        lds_barrier_asm();
         float *const out32 = reinterpret_cast<float *>(parts) + ((int64_t)slice * N + n0) * K + k0;
         for (int e = tid; e < BN * (BK / 4); e += THREADS) {
             const int nl = e / (BK / 4), c = e % (BK / 4);
@@ -196,7 +188,7 @@ __device__ __forceinline__ void dweight_block(const __bf16 *__restrict__ dy, int
                 const int nl = 32 * (NTW * wn + a) + rowof(i, h), kl = 32 * (KTW * wk + b) + r;
                 reinterpret_cast<__bf16 *>(smem)[nl * BK + kl] = (__bf16)acc[a][b][i];
             }
-    lds_barrier();
+    lds_barrier_asm();
     __bf16 *const out = parts + ((int64_t)slice * N + n0) * K + k0;
     for (int e = tid; e < BN * (BK / 8); e += THREADS) {
         const int nl = e / (BK / 8), c = e % (BK / 8);
@@ -233,7 +225,7 @@ extern "C" int g2048_dweight_bf16(const void *dy, int64_t lddy, const void *x, i
                                   int K, int slices, int block_rows, void *stream) {
     if (!dy || !x || !parts || T <= 0 || N < 128 || N % 128 || K < BK || K % BK || slices < 1 || (slices >= 8 && slices % 8) ||
         T % ((int64_t)TOKS * slices) || lddy < N || ldx < K || (lddy & 7) || (ldx & 7) ||
-        (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)parts) & 15) || ((uintptr_t)colsum & 3) || lddy * 2 * 4 >= (1ll << 31) || ldx * 2 * 4 >= (1ll << 31) ||
+        !aligned16(dy, x, parts) || ((uintptr_t)colsum & 3) || lddy * 2 * 4 >= (1ll << 31) || ldx * 2 * 4 >= (1ll << 31) ||
         (block_rows != 0 && block_rows != 128 && block_rows != 256) || (block_rows == 256 && N % 256))
         return G2048_EINVAL;
     const int k_blocks = K / BK;
@@ -243,22 +235,21 @@ extern "C" int g2048_dweight_bf16(const void *dy, int64_t lddy, const void *x, i
     const dim3 grid((unsigned)(slices * (N / bn) * k_blocks));
     const void *fn = wide ? reinterpret_cast<const void *>(k_dweight<2, 4>) : reinterpret_cast<const void *>(k_dweight<1, 4>);
     const int lds = dw_nbuf(bn) * TOKS * (bn + BK) * 2;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -(1000 + (int)hipGetLastError());
+    if (const int rc = allow_dynamic_lds(fn, lds)) return rc;
     if (wide)
         hipLaunchKernelGGL((k_dweight<2, 4>), grid, dim3(512), lds, (hipStream_t)stream, (const __bf16 *)dy, lddy, (const __bf16 *)x, ldx,
                            (__bf16 *)parts, colsum, T, N, K, slices, k_blocks);
     else
         hipLaunchKernelGGL((k_dweight<1, 4>), grid, dim3(512), lds, (hipStream_t)stream, (const __bf16 *)dy, lddy, (const __bf16 *)x, ldx,
                            (__bf16 *)parts, colsum, T, N, K, slices, k_blocks);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
+    return launch_status();
 }
 
 static bool dwg_ok(const void *dy, int64_t lddy, const void *x, int64_t ldx, const void *parts, const float *colsum, int64_t T, int N, int K,
                    int slices) {
     return dy && x && parts && T > 0 && N >= 128 && N % 128 == 0 && K >= BK && K % BK == 0 && slices >= 1 && !(slices >= 8 && slices % 8) &&
            T % ((int64_t)TOKS * slices) == 0 && lddy >= N && ldx >= K && !(lddy & 7) && !(ldx & 7) &&
-           !(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)parts) & 15) && !((uintptr_t)colsum & 3) && lddy * 2 * 4 < (1ll << 31) &&
+           aligned16(dy, x, parts) && !((uintptr_t)colsum & 3) && lddy * 2 * 4 < (1ll << 31) &&
            ldx * 2 * 4 < (1ll << 31);
 }
 
@@ -278,9 +269,7 @@ extern "C" int g2048_dweight_jobs(const g2048_dwg_job *jobs, int n_jobs, void *s
     J.first_block[n_jobs] = (int32_t)blocks;
     if (blocks > 65535 * 16) return G2048_EINVAL;
     const int lds = dw_nbuf(128) * TOKS * (128 + BK) * 2;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_dweight_jobs), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-        return -(1000 + (int)hipGetLastError());
+    if (const int rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_dweight_jobs), lds)) return rc;
     hipLaunchKernelGGL(k_dweight_jobs, dim3((unsigned)blocks), dim3(512), lds, (hipStream_t)stream, J);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
+    return launch_status();
 }

@@ -13,38 +13,20 @@
 #include <stdint.h>
 
 #include "../../include/g2048.h"
+#include "g2048_bits.h"
 #include "g2048_colsum_final.h"
+#include "g2048_host.h"
 
 namespace {
+
+using namespace g2048_bits;
+using namespace g2048_host;
 
 constexpr int D = 256, WAVES = 4;
 // rows per workgroup of the add+LN backward: 32 for the 34 816-token activations (1 088 workgroups: 26.4 us per launch; 64 rows
 // = 544 workgroups 30.8 us; 16 rows no faster and twice the partial rows for g2048_reduce_jobs); 8 for the 2048-row ones of the
 // CLS-only layer (32 workgroups whose waves walk 16 rows each, two dependent wave reductions per row, took 12-16 us for 2 MB)
 __host__ __device__ inline int ln_rows_per_block(int64_t T) { return T >= 16384 ? 32 : 8; }
-
-__device__ __forceinline__ float wave_sum(float v) {
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-__device__ __forceinline__ bool keep_elem(uint32_t s0, uint32_t s1, uint32_t thr, uint64_t idx) {
-    uint32_t x = (uint32_t)idx * 0x9E3779B1u ^ s0;
-    x ^= (uint32_t)(idx >> 32) * 0x85EBCA77u + s1;
-    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-    return (x >> 8) >= thr;
-}
-__device__ __forceinline__ void mix_seed_state(const uint64_t *seed_state, uint32_t &s0, uint32_t &s1) {
-    if (seed_state) {
-        const uint64_t s = *seed_state;
-        s0 ^= (uint32_t)s * 0x9E3779B1u;
-        s1 += (uint32_t)(s >> 32) * 0x85EBCA77u + (uint32_t)s;
-    }
-}
-__device__ __forceinline__ float bf2f(uint32_t hi16) { return __uint_as_float(hi16 << 16); }
-__device__ __forceinline__ uint32_t f2bf(float f) {
-    const __bf16 b = (__bf16)f;
-    return *reinterpret_cast<const uint16_t *>(&b);
-}
 
 // x: f32 rows of 256 with row stride x_rs (elements); a: bf16 [T][256] or null; outputs contiguous [T][256]
 __global__ void __launch_bounds__(64 * WAVES)
@@ -198,18 +180,13 @@ k_add_ln_bwd(const float *__restrict__ xn, int64_t xn_rs, const float *__restric
     }
 }
 
-inline int done() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
-}
-
 }  // namespace
 
 extern "C" int g2048_add_ln_fwd(const float *x, int64_t x_row_stride, const void *a, const float *gamma, const float *beta,
                                 float *x_new, void *h, float *mean, float *rstd, int64_t T, float eps, float p_drop,
                                 uint64_t seed, const uint64_t *seed_state, void *stream) {
     if (!x || !h || T <= 0 || (gamma && (!beta || !mean || !rstd || (a && !x_new))) || !(p_drop >= 0.f && p_drop < 1.f) ||
-        (x_row_stride & 3) || (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)x_new) & 15) ||
+        (x_row_stride & 3) || !aligned16(x, gamma, beta, x_new) ||
         (((uintptr_t)a | (uintptr_t)h) & 7))
         return G2048_EINVAL;
     const uint32_t thr = a ? (uint32_t)(p_drop * 16777216.0f) : 0u;
@@ -219,7 +196,7 @@ extern "C" int g2048_add_ln_fwd(const float *x, int64_t x_row_stride, const void
     hipLaunchKernelGGL(k_add_ln_fwd, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(64 * WAVES), 0, (hipStream_t)stream, x,
                        x_row_stride, (const uint16_t *)a, gamma, beta, x_new, (uint16_t *)h, mean, rstd, T, eps,
                        1.0f / (1.0f - p_drop), thr, (uint32_t)seed, (uint32_t)(seed >> 32), seed_state);
-    return done();
+    return launch_status();
 }
 
 // ---- column sums (bias gradients) ------------------------------------------------------------------------------------
@@ -296,7 +273,7 @@ extern "C" int g2048_colsum(const void *x, int is_bf16, int64_t row_stride, int6
                             void *stream) {
     if (!out && N > CS_THREADS * CS_VEC) return G2048_EINVAL;  // first stage only: one column tile
     if (!x || !workspace || T <= 0 || N < CS_VEC || N % CS_VEC || row_stride % CS_VEC || row_stride < N ||
-        ((uintptr_t)x & (is_bf16 ? 7 : 15)) || ((uintptr_t)workspace & 15))
+        ((uintptr_t)x & (is_bf16 ? 7 : 15)) || !aligned16(workspace))
         return G2048_EINVAL;
     // wider matrices are summed in column tiles of at most CS_THREADS * CS_VEC (1024) columns, each with its own slice of
     // the workspace (MAX_GROUPS * tile floats, so the slices of all tiles fit in MAX_GROUPS * N)
@@ -316,7 +293,7 @@ extern "C" int g2048_colsum(const void *x, int is_bf16, int64_t row_stride, int6
             hipLaunchKernelGGL(k_colsum_final, dim3((unsigned)((n + CF_COLS - 1) / CF_COLS)), dim3(CF_COLS * CF_SLICES), 0,
                                (hipStream_t)stream, ws, (int)G, n, out + c0);
     }
-    return done();
+    return launch_status();
 }
 
 extern "C" int64_t g2048_add_ln_bwd_workspace_floats(int64_t T) {
@@ -328,7 +305,7 @@ extern "C" int g2048_add_ln_bwd(const float *x_norm, int64_t x_row_stride, const
                                 int64_t T, float p_drop, uint64_t seed, const uint64_t *seed_state, int g_x_period, void *stream) {
     if (g_x_period < 1) return G2048_EINVAL;
     if (!g_h || !dx || !workspace || T <= 0 || (x_row_stride & 3) || (gamma && (!x_norm || !mean || !rstd)) ||
-        !(p_drop >= 0.f && p_drop < 1.f) || (((uintptr_t)x_norm | (uintptr_t)g_x | (uintptr_t)dx | (uintptr_t)gamma) & 15) ||
+        !(p_drop >= 0.f && p_drop < 1.f) || !aligned16(x_norm, g_x, dx, gamma) ||
         (((uintptr_t)g_h | (uintptr_t)da) & 7))
         return G2048_EINVAL;
     const uint32_t thr = da ? (uint32_t)(p_drop * 16777216.0f) : 0u;
@@ -339,7 +316,7 @@ extern "C" int g2048_add_ln_bwd(const float *x_norm, int64_t x_row_stride, const
     if (dparams)
         hipLaunchKernelGGL(k_colsum_final, dim3(3 * D / CF_COLS), dim3(CF_COLS * CF_SLICES), 0, (hipStream_t)stream, workspace, (int)blocks,
                            3 * D, dparams);
-    return done();
+    return launch_status();
 }
 
 // ---- feed-forward activation: y = dropout(relu(x)) ----------------------------------------------------------------------
@@ -362,9 +339,9 @@ k_relu_dropout_fwd(const uint4 *__restrict__ x, uint4 *__restrict__ y, int64_t n
         const uint32_t w[4] = {in.x, in.y, in.z, in.w};
         uint32_t o[4];
         for (int q = 0; q < 4; ++q) {
-            uint32_t hsh = (uint32_t)(4 * v + q) * 0x9E3779B1u ^ s0;
-            hsh ^= (uint32_t)((uint64_t)(4 * v + q) >> 32) * 0x85EBCA77u + s1;
-            hsh ^= hsh >> 16; hsh *= 0x7FEB352Du; hsh ^= hsh >> 15; hsh *= 0x846CA68Bu; hsh ^= hsh >> 16;
+            uint32_t hsh = (uint32_t)(4 * v + q) * HASH_MUL ^ s0;
+            hsh ^= (uint32_t)((uint64_t)(4 * v + q) >> 32) * HASH_MUL_HI + s1;
+            G2048_HASH_FIN(hsh);
             const float a = bf2f(w[q] & 0xFFFFu), b = bf2f(w[q] >> 16);
             const float ya = (a > 0.f && (hsh & 0xFFFFu) >= thr16) ? a * inv_keep : 0.f;
             const float yb = (b > 0.f && (hsh >> 16) >= thr16) ? b * inv_keep : 0.f;
@@ -419,14 +396,14 @@ inline bool rd_shape_ok(int64_t T, int F) { return T > 0 && F >= RD_VEC && F % R
 
 extern "C" int g2048_relu_dropout_fwd(const void *x, void *y, int64_t T, int F, float p_drop, uint64_t seed,
                                       const uint64_t *seed_state, void *stream) {
-    if (!x || !y || !rd_shape_ok(T, F) || !(p_drop >= 0.f && p_drop < 1.f) || (((uintptr_t)x | (uintptr_t)y) & 15)) return G2048_EINVAL;
+    if (!x || !y || !rd_shape_ok(T, F) || !(p_drop >= 0.f && p_drop < 1.f) || !aligned16(x, y)) return G2048_EINVAL;
     const int64_t n_vec = T * (F / RD_VEC);
     int64_t blocks = (n_vec + RD_THREADS - 1) / RD_THREADS;
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(k_relu_dropout_fwd, dim3((unsigned)blocks), dim3(RD_THREADS), 0, (hipStream_t)stream, (const uint4 *)x, (uint4 *)y,
                        n_vec, 1.0f / (1.0f - p_drop), (uint32_t)(p_drop * 65536.0f + 0.5f), (uint32_t)seed, (uint32_t)(seed >> 32),
                        seed_state);
-    return done();
+    return launch_status();
 }
 
 extern "C" int64_t g2048_relu_dropout_bwd_workspace_floats(int64_t T, int F) {
@@ -436,7 +413,7 @@ extern "C" int64_t g2048_relu_dropout_bwd_workspace_floats(int64_t T, int F) {
 extern "C" int g2048_relu_dropout_bwd(const void *dy, const void *y, void *dx, float *dbias, float *workspace, int64_t T, int F,
                                       float p_drop, void *stream) {
     if (!dy || !y || !dx || !workspace || !rd_shape_ok(T, F) || !(p_drop >= 0.f && p_drop < 1.f) ||
-        (((uintptr_t)dy | (uintptr_t)y | (uintptr_t)dx | (uintptr_t)workspace) & 15))
+        !aligned16(dy, y, dx, workspace))
         return G2048_EINVAL;
     const int64_t blocks = (T + rd_rows_per_block(T) - 1) / rd_rows_per_block(T);
     hipLaunchKernelGGL(k_relu_dropout_bwd, dim3((unsigned)blocks), dim3(RD_THREADS), 0, (hipStream_t)stream, (const uint4 *)dy,
@@ -444,7 +421,7 @@ extern "C" int g2048_relu_dropout_bwd(const void *dy, const void *y, void *dx, f
     if (dbias)
         hipLaunchKernelGGL(k_colsum_final, dim3((unsigned)((F + CF_COLS - 1) / CF_COLS)), dim3(CF_COLS * CF_SLICES), 0, (hipStream_t)stream,
                            workspace, (int)blocks, F, dbias);
-    return done();
+    return launch_status();
 }
 
 // ---- token embedding of packed boards (update) ---------------------------------------------------------------------------
@@ -581,7 +558,7 @@ k_embed_bwd(const uint8_t *__restrict__ boards, const float *__restrict__ dx0, f
 extern "C" int g2048_embed_fwd(const uint8_t *boards, const float *wt, int w_ld, const float *pe, const float *cls, float *x0, int64_t M,
                                float p_drop, uint64_t seed, const uint64_t *seed_state, void *stream) {
     if (!boards || !wt || !pe || !cls || !x0 || M <= 0 || !(p_drop >= 0.f && p_drop < 1.f) || (w_ld != 0 && w_ld < 31) ||
-        (((uintptr_t)pe | (uintptr_t)cls | (uintptr_t)x0) & 15) || ((uintptr_t)wt & (w_ld ? 3 : 15)))
+        !aligned16(pe, cls, x0) || ((uintptr_t)wt & (w_ld ? 3 : 15)))
         return G2048_EINVAL;
     const int64_t n_rows = M * EMB_SEQ;
     int64_t blocks = (n_rows + 3) / 4;
@@ -589,14 +566,14 @@ extern "C" int g2048_embed_fwd(const uint8_t *boards, const float *wt, int w_ld,
     hipLaunchKernelGGL(k_embed_fwd<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, boards, wt, w_ld, pe, cls, x0, n_rows,
                        1.0f / (1.0f - p_drop), (uint32_t)(p_drop * 16777216.0f), (uint32_t)seed, (uint32_t)(seed >> 32), seed_state,
                        EmbedLN{});
-    return done();
+    return launch_status();
 }
 
 extern "C" int g2048_embed_ln_fwd(const uint8_t *boards, const float *wt, int w_ld, const float *pe, const float *cls, float *x0, int64_t M,
                                   float p_drop, uint64_t seed, const uint64_t *seed_state, const float *gamma, const float *beta, float eps,
                                   void *h, float *mean, float *rstd, void *stream) {
     if (!boards || !wt || !pe || !cls || !x0 || M <= 0 || !(p_drop >= 0.f && p_drop < 1.f) || (w_ld != 0 && w_ld < 31) || !gamma || !beta ||
-        !h || !mean || !rstd || (((uintptr_t)pe | (uintptr_t)cls | (uintptr_t)x0 | (uintptr_t)gamma | (uintptr_t)beta) & 15) ||
+        !h || !mean || !rstd || !aligned16(pe, cls, x0, gamma, beta) ||
         ((uintptr_t)h & 7) || ((uintptr_t)wt & (w_ld ? 3 : 15)))
         return G2048_EINVAL;
     const int64_t n_rows = M * EMB_SEQ;
@@ -606,7 +583,7 @@ extern "C" int g2048_embed_ln_fwd(const uint8_t *boards, const float *wt, int w_
     L.gamma = gamma, L.beta = beta, L.h = (uint16_t *)h, L.mean = mean, L.rstd = rstd, L.eps = eps;
     hipLaunchKernelGGL(k_embed_fwd<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, boards, wt, w_ld, pe, cls, x0, n_rows,
                        1.0f / (1.0f - p_drop), (uint32_t)(p_drop * 16777216.0f), (uint32_t)seed, (uint32_t)(seed >> 32), seed_state, L);
-    return done();
+    return launch_status();
 }
 
 extern "C" int64_t g2048_embed_bwd_workspace_floats(int64_t M) { return M <= 0 ? 0 : (int64_t)EMB_BLOCKS * EMB_CLASSES * EMB_D; }
@@ -614,17 +591,16 @@ extern "C" int64_t g2048_embed_bwd_workspace_floats(int64_t M) { return M <= 0 ?
 extern "C" int g2048_embed_bwd(const uint8_t *boards, const float *dx0, float *dwt_dcls, float *workspace, int64_t M, float p_drop,
                                uint64_t seed, const uint64_t *seed_state, void *stream) {
     if (!boards || !dx0 || !workspace || M <= 0 || !(p_drop >= 0.f && p_drop < 1.f) ||
-        (((uintptr_t)dx0 | (uintptr_t)dwt_dcls | (uintptr_t)workspace) & 15))
+        !aligned16(dx0, dwt_dcls, workspace))
         return G2048_EINVAL;
     // per call, not latched: the attribute is per device, and a latch would be the library's only global state
     const int lds = 4 * EMB_CLASSES * EMB_D * (int)sizeof(float);
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_embed_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-        return -(1000 + (int)hipGetLastError());
+    if (const int rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_embed_bwd), lds)) return rc;
     const int64_t n_rows = M * EMB_SEQ;
     hipLaunchKernelGGL(k_embed_bwd, dim3(EMB_BLOCKS), dim3(256), lds, (hipStream_t)stream, boards, dx0, workspace, n_rows,
                        1.0f / (1.0f - p_drop), (uint32_t)(p_drop * 16777216.0f), (uint32_t)seed, (uint32_t)(seed >> 32), seed_state);
     if (dwt_dcls)
         hipLaunchKernelGGL(k_colsum_final, dim3(EMB_CLASSES * EMB_D / CF_COLS), dim3(CF_COLS * CF_SLICES), 0, (hipStream_t)stream,
                            workspace, EMB_BLOCKS, EMB_CLASSES * EMB_D, dwt_dcls);
-    return done();
+    return launch_status();
 }

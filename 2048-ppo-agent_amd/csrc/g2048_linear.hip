@@ -26,8 +26,13 @@
 
 #include "../../include/g2048.h"
 #include "g2048_colsum_final.h"
+#include "g2048_host.h"
+#include "g2048_mfma.h"
 
 namespace {
+
+using namespace g2048_mfma;
+using namespace g2048_host;
 
 enum { EPI_NONE = 0, EPI_RELU_DROPOUT = 1, EPI_MASK_COLSUM = 2 };
 struct Epi {
@@ -41,17 +46,9 @@ struct Epi {
     uint32_t hi_term;               // EPI_RELU_DROPOUT: contribution of the seed's high word, constant per launch
 };
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int TOK = 128, NS = 128, KC = 128, THREADS = 256;
 constexpr int CHUNK_BYTES = NS * KC * 2;  // one K-chunk of the weight slice: 32 KiB
 constexpr int NBUF = 2;
-
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-    const __bf16 x = (__bf16)a, y = (__bf16)b;
-    return (uint32_t) * reinterpret_cast<const uint16_t *>(&x) | ((uint32_t) * reinterpret_cast<const uint16_t *>(&y) << 16);
-}
 
 // LDS image of a chunk: [128 rows n][16 chunks of 16 B], chunk q of row r stored at q ^ (r & 15).
 // DMA: wave-instruction t of wave w fills LDS bytes [(4t + w) * 1024, +1024) = rows 4(4t + w) .. +3; lane i supplies
@@ -88,8 +85,8 @@ __device__ __forceinline__ void store_tile(f32x16 acc[4], const float *__restric
             for (int i = 0; i < 16; i += 2) {
                 float a = fmaxf(acc[j][i], 0.f), b = fmaxf(acc[j][i + 1], 0.f);
                 if (E.thr16) {  // one 32-bit hash per pair of neighbouring columns, 16 bits each
-                    uint32_t x = (pair0 + (uint32_t)(16 * j + ((i & 3) >> 1) + 4 * (i >> 2))) * 0x9E3779B1u + E.hi_term;
-                    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
+                    uint32_t x = (pair0 + (uint32_t)(16 * j + ((i & 3) >> 1) + 4 * (i >> 2))) * HASH_MUL + E.hi_term;
+                    G2048_HASH_FIN(x);
                     a = (x & 0xFFFFu) >= E.thr16 ? a * E.inv_keep : 0.f;
                     b = (x >> 16) >= E.thr16 ? b * E.inv_keep : 0.f;
                 }
@@ -195,29 +192,6 @@ k_linear(const __bf16 *__restrict__ x, int64_t ldx, const __bf16 *__restrict__ w
 // One workgroup per CU (2 x 32 KiB of X + 32 KiB of staging + bias + mask words); the order of fetch, MFMAs, epilogue, wait and stores
 // inside the tile loop is what the comment in front of k_linear_ws is about.
 // Accumulator tile of wave w, token block b: acc[b][i] = Y^T[n0 + 32 w + rowof(i, h)][token 32 b + r].
-__device__ __forceinline__ int rowof(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-
-// One LDS-DMA wave-instruction (BYTES per lane, lane l lands at lds + BYTES l), written as inline assembly ON PURPOSE: for the builtin
-// the compiler's wait-count pass makes every later LDS read of the wave wait for the DMA (it cannot tell the buffers of one dynamic
-// LDS array apart), i.e. `s_waitcnt vmcnt(0)` right after the fetch that is meant to stay in flight for a whole tile.  The waits for
-// these fetches are therefore all explicit (`s_waitcnt vmcnt(0)` + barrier in k_linear_ws).  Unknown to the compiler, they can only
-// make ITS counted waits longer, never shorter (vmcnt retires in order and they are younger than what it waits for or it waits for 0).
-// (m0 is "reserved" for the compiler; it writes it only right in front of its own LDS-DMA builtins, which this kernel does not use)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-template <int BYTES>
-__device__ __forceinline__ void dma_async(const void *g, void *lds) {
-    const uint32_t l = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)lds);
-    if (BYTES == 16) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(l) : "memory", "m0");
-    else asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(g), "s"(l) : "memory", "m0");
-}
-
-// the same with a scalar base and a 32-bit per-lane offset: no vector arithmetic per instruction
-__device__ __forceinline__ void dma_async16(const void *sbase, uint32_t voff, void *lds) {
-    const uint32_t l = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)lds);
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(l) : "memory", "m0");
-}
-#pragma clang diagnostic pop
 
 // X tile [64 tokens][K] -> LDS rows of K * 2 bytes, chunk q of row r at q ^ (r & 15); K = 256: 32 wave-instructions of 1 KiB (2 rows
 // each), dealt to the workgroup's NF waves: wave f issues instructions f, f + NF, ...
@@ -260,37 +234,14 @@ struct XTileDma {
 #ifdef G2048_WS_STAMPS
 constexpr int WS_PHASES = 8;
 __device__ unsigned long long g_ws_stamps[2][WS_PHASES];
-struct WsStamps {
-    unsigned long long last, acc[WS_PHASES];
-    __device__ __forceinline__ static unsigned long long now() {
-        unsigned long long t;
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-        __builtin_amdgcn_sched_barrier(0);
-        return t;
-    }
-    __device__ __forceinline__ void start() {
-        for (int i = 0; i < WS_PHASES; ++i) acc[i] = 0;
-        last = now();
-    }
-    __device__ __forceinline__ void mark(int k) {
-        const unsigned long long t = now();
-        acc[k] += t - last;
-        last = t;
-    }
-    __device__ __forceinline__ void flush(int lane, int w) {
-        if (lane == 0 && w < 2 && blockIdx.y == 0 && blockIdx.x % 16 == 0)
-            for (int i = 0; i < WS_PHASES; ++i) atomicAdd(&g_ws_stamps[w == 0 ? 0 : 1][i], acc[i]);
-    }
+struct WsStampSite {
+    __device__ __forceinline__ static bool on(int lane, int w) { return lane == 0 && w < 2 && blockIdx.y == 0 && blockIdx.x % 16 == 0; }
+    __device__ __forceinline__ static unsigned long long *table(int w) { return g_ws_stamps[w == 0 ? 0 : 1]; }
 };
 #define WS_STAMP(k) stamps.mark(k)
 #else
 #define WS_STAMP(k)
 #endif
-
-// workgroup barrier that waits for this wave's LDS traffic only: __syncthreads() also drains vmcnt, i.e. would make the storing waves
-// wait for their global stores at every barrier
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // The loop of a workgroup over its 64-token tiles (round 3, final form).  A wave's vmcnt counts loads AND stores, so "wait for my
 // fetch" right after "store my share of the previous tile" waits for the stores too (measured: double buffering with the wait at the top
@@ -350,12 +301,8 @@ k_linear_ws(const __bf16 *__restrict__ x, int64_t ldx, const __bf16 *__restrict_
     uint32_t *const bits_l = reinterpret_cast<uint32_t *>(smem + NB * xbytes + sbytes + NSW * 4);  // [NB][THREADS]
     for (int i = tid; i < NSW; i += THREADS) bias_l[i] = HAS_BIAS ? bias[n0 + i] : 0.f;
     if (EPI == EPI_RELU_DROPOUT) {
-        if (E.seed_state) {
-            const uint64_t sd = *E.seed_state;  // same mixing as the other dropout kernels (g2048_layernorm.hip)
-            E.s0 ^= (uint32_t)sd * 0x9E3779B1u;
-            E.s1 += (uint32_t)(sd >> 32) * 0x85EBCA77u + (uint32_t)sd;
-        }
-        E.hi_term = E.s0 ^ (E.s1 * 0x85EBCA77u);
+        mix_seed_state(E.seed_state, E.s0, E.s1);
+        E.hi_term = E.s0 ^ (E.s1 * HASH_MUL_HI);
     }
     const int slices = gridDim.y;
     float colacc[EPI == EPI_MASK_COLSUM ? 16 : 1];  // per-lane sums over this workgroup's tokens of the lane's output rows
@@ -378,14 +325,14 @@ k_linear_ws(const __bf16 *__restrict__ x, int64_t ldx, const __bf16 *__restrict_
     if ((int64_t)blockIdx.x < n_tiles64) fetch(blockIdx.x, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the first barrier 1 publishes the first tile)
 #ifdef G2048_WS_STAMPS
-    WsStamps stamps;
+    Stamps<WS_PHASES, WsStampSite> stamps;
     stamps.start();
 #endif
     int buf = 0;
     for (int64_t tile = blockIdx.x; tile < n_tiles64; tile += gridDim.x, buf ^= 1) {
         const int64_t tok0 = tile * TOKW;
         const char *const xb = smem + buf * xbytes;
-        lds_barrier();  // every wave is done with the staging tile (its reads for the copy-out of the previous tile)
+        lds_barrier_asm();  // every wave is done with the staging tile (its reads for the copy-out of the previous tile)
         WS_STAMP(1);
         if (tile + gridDim.x < n_tiles64) fetch(tile + gridDim.x, buf ^ 1);
         WS_STAMP(2);
@@ -404,8 +351,8 @@ k_linear_ws(const __bf16 *__restrict__ x, int64_t ldx, const __bf16 *__restrict_
         // the seed's high word through E.hi_term: the convention of the round-2 kernel); p = 0: thr16 = 0 keeps everything
         auto keep_pair = [&](int pi, uint32_t pair0) -> uint32_t {  // bit 0 / 1: column i / i + 1 is kept
             const int i = 2 * pi;
-            uint32_t xh = (pair0 + (uint32_t)(((i & 3) >> 1) + 4 * (i >> 2))) * 0x9E3779B1u + E.hi_term;
-            xh ^= xh >> 16; xh *= 0x7FEB352Du; xh ^= xh >> 15; xh *= 0x846CA68Bu; xh ^= xh >> 16;
+            uint32_t xh = (pair0 + (uint32_t)(((i & 3) >> 1) + 4 * (i >> 2))) * HASH_MUL + E.hi_term;
+            G2048_HASH_FIN(xh);
             return ((xh & 0xFFFFu) >= E.thr16 ? 1u : 0u) | ((xh >> 16) >= E.thr16 ? 2u : 0u);
         };
         auto drop_pair = [&](int b, int pi, uint32_t keep) {
@@ -491,7 +438,7 @@ k_linear_ws(const __bf16 *__restrict__ x, int64_t ldx, const __bf16 *__restrict_
         WS_STAMP(5);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // my part of the next tile has landed; my stores of the previous tile are out
         WS_STAMP(0);
-        lds_barrier();  // the output tile is complete, the next X tile is published
+        lds_barrier_asm();  // the output tile is complete, the next X tile is published
         WS_STAMP(6);
         {
             constexpr int PIECES = TOKW * CPR_Y, STORERS = THREADS, ROUNDS = PIECES / STORERS;
@@ -547,7 +494,7 @@ inline int64_t ws_groups(int64_t T, int N) {
 inline bool operands_ok(const void *x, int64_t ldx, const void *weight, int64_t ldw, const void *y, int64_t ldy, int64_t T, int K,
                         int N, const void *bias) {
     return x && weight && y && T > 0 && K >= KC && K % KC == 0 && N >= NS && N % NS == 0 && ldx >= K && ldw >= K && ldy >= N &&
-           !(ldx & 7) && !(ldw & 7) && !(ldy & 7) && !(((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y | (uintptr_t)bias) & 15);
+           !(ldx & 7) && !(ldw & 7) && !(ldy & 7) && aligned16(x, weight, y, bias);
 }
 
 // K <= 256: weights-stationary kernel; 256-wide slices (8 waves, one workgroup per CU) when N allows, else 128-wide (4 waves, two per CU)
@@ -558,11 +505,10 @@ int launch_ws(const __bf16 *x, int64_t ldx, const __bf16 *w, int64_t ldw, const 
     // two X buffers + the output staging tile + bias + mask words
     const int lds = 2 * TOKW * 16 * KS * 2 + TOKW * 2 * 32 * WAVES + 32 * WAVES * 4 + 2 * 64 * WAVES * 4;
     // the dynamic-LDS limit is a per-device attribute of the one kernel this call launches: set per call, no latch
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -(1000 + (int)hipGetLastError());
+    if (const int rc = allow_dynamic_lds(fn, lds)) return rc;
     hipLaunchKernelGGL((k_linear_ws<HAS_BIAS, EPI, KS, WAVES>), dim3((unsigned)groups, (unsigned)(N / (32 * WAVES))), dim3(64 * WAVES), lds,
                        stream, x, ldx, w, ldw, bias, y, ldy, T, E);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
+    return launch_status();
 }
 template <bool HAS_BIAS, int EPI>
 int launch_stationary(const __bf16 *x, int64_t ldx, const __bf16 *w, int64_t ldw, const float *bias, __bf16 *y, int64_t ldy, int64_t T,
@@ -589,16 +535,14 @@ extern "C" int g2048_linear_bf16(const void *x, int64_t ldx, const void *weight,
         return bias ? launch_stationary<true, EPI_NONE>(xp, ldx, wp, ldw, bias, yp, ldy, T, K, N, Epi{}, nullptr, (hipStream_t)stream)
                     : launch_stationary<false, EPI_NONE>(xp, ldx, wp, ldw, bias, yp, ldy, T, K, N, Epi{}, nullptr, (hipStream_t)stream);
     const void *fn = bias ? reinterpret_cast<const void *>(k_linear<true>) : reinterpret_cast<const void *>(k_linear<false>);
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, NBUF * CHUNK_BYTES) != hipSuccess)
-        return -(1000 + (int)hipGetLastError());
+    if (const int rc = allow_dynamic_lds(fn, NBUF * CHUNK_BYTES)) return rc;
     const dim3 grid((unsigned)((T + TOK - 1) / TOK), (unsigned)(N / NS));
     if (bias)
         hipLaunchKernelGGL(k_linear<true>, grid, dim3(THREADS), NBUF * CHUNK_BYTES, (hipStream_t)stream, xp, ldx, wp, ldw, bias, yp, ldy, T, K);
     else
         hipLaunchKernelGGL(k_linear<false>, grid, dim3(THREADS), NBUF * CHUNK_BYTES, (hipStream_t)stream, xp, ldx, wp, ldw, bias, yp, ldy, T,
                            K);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
+    return launch_status();
 }
 
 extern "C" int64_t g2048_ffn_mask_bytes(int64_t T, int N) {
@@ -635,7 +579,7 @@ extern "C" int g2048_linear_mask_bwd_bf16(const void *dy, int64_t lddy, const vo
                                           void *dz, int64_t lddz, float *dbias, float *workspace, int64_t T, int K, int N,
                                           float p_drop, void *stream) {
     if (!operands_ok(dy, lddy, weight_t, ldw, dz, lddz, T, K, N, nullptr) || K > NBUF * KC || !mask_bits ||
-        ((uintptr_t)mask_bits & 7) || !workspace || ((uintptr_t)workspace & 15) || !(p_drop >= 0.f && p_drop < 1.f))
+        ((uintptr_t)mask_bits & 7) || !workspace || !aligned16(workspace) || !(p_drop >= 0.f && p_drop < 1.f))
         return G2048_EINVAL;
     Epi E{};
     E.inv_keep = 1.0f / (1.0f - p_drop);
@@ -648,8 +592,7 @@ extern "C" int g2048_linear_mask_bwd_bf16(const void *dy, int64_t lddy, const vo
     if (rc || !dbias) return rc;  // dbias NULL: the partial rows stay in the workspace for g2048_reduce_jobs
     hipLaunchKernelGGL(k_colsum_final, dim3((unsigned)((N + CF_COLS - 1) / CF_COLS)), dim3(CF_COLS * CF_SLICES), 0, (hipStream_t)stream,
                        workspace, groups, N, dbias);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
+    return launch_status();
 }
 
 #ifdef G2048_WS_STAMPS

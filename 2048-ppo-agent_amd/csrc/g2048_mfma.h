@@ -1,7 +1,11 @@
-// MFMA building blocks shared by the fused update kernels (csrc/g2048_tail.hip, csrc/g2048_block.hip): fragment layouts of
-// v_mfma_f32_32x32x16_bf16, the fragment-packed weight layout, the register ring that streams weight units ahead of their MFMAs,
-// LDS activation tiles, the update's dropout hash.  Device code only; included inside the including file's anonymous namespace
-// users via `using namespace g2048_mfma`.
+// MFMA and LDS building blocks shared by the HIP translation units: vector typedefs, the fragment layouts of
+// v_mfma_f32_32x32x16_bf16, compile-time loops and scheduling fences, the LDS-DMA wrappers, LDS-only barriers, the cycle-stamp
+// struct of the diagnostic builds; then what the fused update kernels (csrc/g2048_tail.hip, g2048_rowgemm.hip, g2048_mlp.hip) add:
+// the register ring that streams fragment-packed weight units ahead of their MFMAs and LDS activation tiles.
+// Scalar helpers (bf16 bits, dropout hash, packed_off) live in csrc/g2048_bits.h and are visible through this namespace.
+// Device code only; users write `using namespace g2048_mfma` inside their anonymous namespace, or `using` declarations for single
+// names where a file has shapes of its own under the same name (csrc/g2048_policy.hip: bias_tile, gemm_tile).
+// Helpers that share a name elsewhere but not a body keep distinct names here (lds_barrier / lds_barrier_asm).
 #ifndef G2048_MFMA_H
 #define G2048_MFMA_H
 #include <hip/hip_runtime.h>
@@ -9,59 +13,103 @@
 
 #include <type_traits>
 
+#include "g2048_bits.h"
+
 namespace g2048_mfma {
+
+using namespace g2048_bits;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // accumulator register i of lane (r, h) holds row rowof(i, h), column r of a 32 x 32 tile
 __device__ __forceinline__ int rowof(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 __device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
-__device__ __forceinline__ float wave_sum(float v) {
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
+
+// compile-time loop: f(integral_constant<int, I>) for I = I0..N-1, every index a constant (register arrays stay registers,
+// `if constexpr` on the step number prunes the body per step)
+template <int I, int N, class Fn>
+__device__ __forceinline__ void static_for(Fn &&f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        static_for<I + 1, N>(f);
+    }
 }
-// the update's dropout hash (same function as csrc/g2048_layernorm.hip)
-__device__ __forceinline__ bool keep_elem(uint32_t s0, uint32_t s1, uint32_t thr, uint64_t idx) {
-    uint32_t x = (uint32_t)idx * 0x9E3779B1u ^ s0;
-    x ^= (uint32_t)(idx >> 32) * 0x85EBCA77u + s1;
-    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-    return (x >> 8) >= thr;
+// nothing is scheduled across this point
+__device__ __forceinline__ void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
+
+// ---- LDS-DMA ----------------------------------------------------------------------------------------------------------
+// One LDS-DMA wave-instruction (BYTES per lane, lane l lands at lds + BYTES l), written as inline assembly ON PURPOSE: for the builtin
+// the compiler's wait-count pass makes every later LDS read of the wave wait for the DMA (it cannot tell the buffers of one dynamic
+// LDS array apart), i.e. `s_waitcnt vmcnt(0)` right after the fetch that is meant to stay in flight for a whole tile.  The waits for
+// these fetches are therefore all explicit in the kernels that use them (`s_waitcnt vmcnt(0)` + barrier).  Unknown to the compiler,
+// they can only make ITS counted waits longer, never shorter (vmcnt retires in order and they are younger than what it waits for or it
+// waits for 0).
+// (m0 is "reserved" for the compiler; it writes it only right in front of its own LDS-DMA builtins, which these kernels do not use)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+__device__ __forceinline__ uint32_t lds_addr(void *lds) {  // wave-uniform LDS byte address, in a scalar register
+    return __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)lds);
 }
-struct Drop {
-    uint32_t s0, s1, thr;
-    float inv_keep;
-    __device__ __forceinline__ Drop site(uint32_t k) const { return Drop{s0 + k * 0x632BE5ABu, s1 ^ (k * 0x7F4A7C15u), thr, inv_keep}; }
-    // four consecutive elements idx .. idx + 3 (idx a multiple of 4): one hash per PAIR, its two 16-bit halves compared with the
-    // threshold at 16-bit resolution (the convention of g2048_relu_dropout_fwd): half the vector instructions of four full hashes
-    __device__ __forceinline__ void apply4(float v[4], uint64_t idx) const {
-        if (!thr) return;
-        const uint32_t thr16 = thr >> 8;
-        for (int pr = 0; pr < 2; ++pr) {
-            const uint64_t id = (idx >> 1) + pr;
-            uint32_t x = (uint32_t)id * 0x9E3779B1u ^ s0;
-            x ^= (uint32_t)(id >> 32) * 0x85EBCA77u + s1;
-            x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-            v[2 * pr] = (x & 0xFFFFu) >= thr16 ? v[2 * pr] * inv_keep : 0.0f;
-            v[2 * pr + 1] = (x >> 16) >= thr16 ? v[2 * pr + 1] * inv_keep : 0.0f;
-        }
+template <int BYTES>
+__device__ __forceinline__ void dma_async(const void *g, void *lds) {
+    const uint32_t l = lds_addr(lds);
+    if (BYTES == 16) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(l) : "memory", "m0");
+    else asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(g), "s"(l) : "memory", "m0");
+}
+// 16 bytes per lane with a scalar base and a 32-bit per-lane byte offset: no vector address arithmetic per instruction
+__device__ __forceinline__ void dma16(const void *sbase, uint32_t voff, uint32_t lds_address) {
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_address) : "memory", "m0");
+}
+__device__ __forceinline__ void dma_async16(const void *sbase, uint32_t voff, void *lds) { dma16(sbase, voff, lds_addr(lds)); }
+#pragma clang diagnostic pop
+
+// ---- LDS-only workgroup barriers: __syncthreads() also drains vmcnt, i.e. waits for the global fetches that are meant to stay in
+// flight and for the wave's global stores.  Two bodies on purpose.
+// builtin barrier + scheduling fence (tail, rowgemm, mlp)
+__device__ __forceinline__ void lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    sched_fence();
+}
+// wait and barrier as ONE asm statement, no scheduling fence (linear, dweight)
+__device__ __forceinline__ void lds_barrier_asm() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// ---- cycle stamps of the diagnostic builds (tools/stamps_encoder.py, tools/stamps_linear.py; never in the product library):
+// s_memtime at phase boundaries, summed per phase in scalar registers; at kernel exit the waves with Site::on(lane, w) add
+// their sums to Site::table(w)
+template <int N, class Site>
+struct Stamps {
+    unsigned long long last, acc[N];
+    __device__ __forceinline__ static unsigned long long now() {
+        unsigned long long t;
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+        __builtin_amdgcn_sched_barrier(0);
+        return t;
+    }
+    __device__ __forceinline__ void start() {
+        for (int i = 0; i < N; ++i) acc[i] = 0;
+        last = now();
+    }
+    __device__ __forceinline__ void mark(int k) {
+        const unsigned long long t = now();
+        acc[k] += t - last;
+        last = t;
+    }
+    __device__ __forceinline__ void flush(int lane, int w) {
+        if (Site::on(lane, w))
+            for (int i = 0; i < N; ++i) atomicAdd(&Site::table(w)[i], acc[i]);
     }
 };
-__device__ __forceinline__ Drop make_drop(uint64_t seed, const uint64_t *seed_state, float p_drop) {
-    uint32_t s0 = (uint32_t)seed, s1 = (uint32_t)(seed >> 32);
-    if (seed_state) {
-        const uint64_t s = *seed_state;
-        s0 ^= (uint32_t)s * 0x9E3779B1u;
-        s1 += (uint32_t)(s >> 32) * 0x85EBCA77u + (uint32_t)s;
-    }
-    return Drop{s0, s1, (uint32_t)(p_drop * 16777216.0f), 1.0f / (1.0f - p_drop)};
-}
 
+// ---- fused update kernels: accumulator tiles, LDS activation tiles, the weight ring ------------------------------------------
 // acc[i] = b[row0 + rowof(i, h)]: the bias enters through the accumulator's initial value
 __device__ __forceinline__ f32x16 bias_tile(const float *b, int row0, int h) {
     f32x16 a;
@@ -101,31 +149,9 @@ __device__ __forceinline__ void put4(char *buf, int stride, int r, int col, cons
     for (int q = 0; q < 4; ++q) pk[q] = (__bf16)v[q];
     *reinterpret_cast<bf16x4 *>(buf + r * stride + 2 * col) = pk;
 }
-// Fragment-packed layout of a bf16 matrix X[rows][cols] (rows % 32 == 0, cols % 16 == 0), the order in which a wavefront reads
-// it as an MFMA operand: for every 32-row tile and every 16-column k-step, 64 lanes x 16 bytes = 1 KB contiguous,
-//   offset(row, col) = ((((row / 32) * (cols / 16) + col / 16) * 2 + (col / 8) % 2) * 32 + row % 32) * 8 + col % 8.
-// Row-major operands make every lane of a fragment load touch a different cache line (lane = row): 64 requests of 16 bytes per
-// instruction, measured ~8 B/clk per CU; packed, one instruction is one contiguous KB.
-__device__ __forceinline__ int64_t packed_off(int row, int64_t col, int64_t cols) {
-    return ((((int64_t)(row >> 5) * (cols >> 4) + (col >> 4)) * 2 + ((col >> 3) & 1)) * 32 + (row & 31)) * 8 + (col & 7);
-}
 constexpr int RING = 3, DIST = 2;  // RING = DIST + 1: the slot of unit i + DIST was last read by unit i - 1
 
-template <int I, int N, class Fn>
-__device__ __forceinline__ void static_for(Fn &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-__device__ __forceinline__ void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
-// LDS-only barrier: __syncthreads() would also wait for the weight fetches that are meant to stay in flight (vmcnt(0))
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    sched_fence();
-}
+
 struct Ring {
     bf16x8 a[RING][16];
 };

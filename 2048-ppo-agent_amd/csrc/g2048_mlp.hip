@@ -18,21 +18,14 @@
 #include <stdint.h>
 
 #include "../../include/g2048.h"
+#include "g2048_host.h"
 #include "g2048_mfma.h"
 
 namespace {
 
 using namespace g2048_mfma;
+using namespace g2048_host;
 
-__device__ __forceinline__ float bf2f(uint32_t hi16) { return __uint_as_float(hi16 << 16); }
-__device__ __forceinline__ uint32_t f2bf(float f) {
-    const __bf16 b = (__bf16)f;
-    return *reinterpret_cast<const uint16_t *>(&b);
-}
-inline int mlp_done() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
-}
 
 // ---- trunk_in forward ---------------------------------------------------------------------------------------------------
 // wt: bf16 [496][512] = the TRANSPOSE of trunk_in.weight [512][496] (class-major: row 31 c + v is what cell c holding exponent v adds);
@@ -100,8 +93,6 @@ struct GemmJobs {
     int32_t n_jobs;
     int64_t M;
 };
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 __global__ void __launch_bounds__(GJ_THREADS)
 k_gemm_jobs(GemmJobs J) {
@@ -293,11 +284,11 @@ k_mlp_out_bwd(const float *__restrict__ dlogits, const float *__restrict__ dvalu
 }  // namespace
 
 extern "C" int g2048_mlp_embed_fwd(const uint8_t *boards, const void *wt, const float *bias, void *y, void *onehot, int64_t M, void *stream) {
-    if (!boards || !wt || !bias || !y || M <= 0 || (((uintptr_t)boards | (uintptr_t)wt | (uintptr_t)bias | (uintptr_t)y | (uintptr_t)onehot) & 15))
+    if (!boards || !wt || !bias || !y || M <= 0 || !aligned16(boards, wt, bias, y, onehot))
         return G2048_EINVAL;
     hipLaunchKernelGGL(k_mlp_embed_fwd, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, boards, (const uint16_t *)wt, bias,
                        (uint16_t *)y, (uint16_t *)onehot, M);
-    return mlp_done();
+    return launch_status();
 }
 
 extern "C" int g2048_gemm_jobs(const g2048_gemm_job *jobs, int n_jobs, int64_t M, void *stream) {
@@ -323,14 +314,14 @@ extern "C" int g2048_gemm_jobs(const g2048_gemm_job *jobs, int n_jobs, int64_t M
     const int64_t mt = (M + GJ_TM - 1) / GJ_TM;
     if (mt > 0x7FFFFFFF || tiles > 65535) return G2048_EINVAL;
     hipLaunchKernelGGL(k_gemm_jobs, dim3((unsigned)mt, (unsigned)tiles), dim3(GJ_THREADS), 0, (hipStream_t)stream, J);
-    return mlp_done();
+    return launch_status();
 }
 
 extern "C" int g2048_mlp_out_fwd(const void *h2, const void *w3, float *logits, float *values, int64_t M, void *stream) {
-    if (!h2 || !w3 || !logits || !values || M <= 0 || ((uintptr_t)logits & 15) || (((uintptr_t)h2 | (uintptr_t)w3) & 1)) return G2048_EINVAL;
+    if (!h2 || !w3 || !logits || !values || M <= 0 || !aligned16(logits) || (((uintptr_t)h2 | (uintptr_t)w3) & 1)) return G2048_EINVAL;
     hipLaunchKernelGGL(k_mlp_out_fwd, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)h2,
                        (const uint16_t *)w3, logits, values, M);
-    return mlp_done();
+    return launch_status();
 }
 
 extern "C" int64_t g2048_mlp_out_bwd_partial_rows(int64_t M) { return M <= 0 ? 0 : (M + MO_ROWS - 1) / MO_ROWS; }
@@ -340,5 +331,5 @@ extern "C" int g2048_mlp_out_bwd(const float *dlogits, const float *dvalues, con
     if (!dlogits || !dvalues || !h2 || !w3 || !dh2 || !partial || M <= 0 || (((uintptr_t)partial | (uintptr_t)h2 | (uintptr_t)w3 | (uintptr_t)dh2) & 7)) return G2048_EINVAL;
     hipLaunchKernelGGL(k_mlp_out_bwd, dim3((unsigned)((M + MO_ROWS - 1) / MO_ROWS)), dim3(256), 0, (hipStream_t)stream, dlogits, dvalues,
                        (const uint16_t *)h2, (const uint16_t *)w3, (uint16_t *)dh2, partial, M);
-    return mlp_done();
+    return launch_status();
 }

@@ -18,8 +18,13 @@
 #include <stdint.h>
 
 #include "../../include/g2048.h"
+#include "g2048_bits.h"
+#include "g2048_host.h"
 
 namespace {
+
+using namespace g2048_bits;
+using namespace g2048_host;
 
 constexpr int OPT_THREADS = 256;
 constexpr int OPT_VEC = 4;
@@ -99,32 +104,24 @@ __device__ __forceinline__ void adamw1(float &p, float g, float &m, float &v, fl
 // bf16 shadows of the parameters the update path multiplies with (dense copy and, for the weights whose input gradient is
 // computed by our own GEMM, a transposed copy): rewritten here, in the kernel that changes the parameter, instead of by cast
 // and transpose kernels in front of every forward
-__device__ __forceinline__ uint16_t to_bf16(float f) {
-    const __bf16 b = (__bf16)f;
-    return *reinterpret_cast<const uint16_t *>(&b);
-}
-// offset of element (row, col) of a [rows][cols] matrix in the fragment-packed layout (include/g2048.h)
-__device__ __forceinline__ int64_t packed_off(int64_t row, int64_t col, int64_t cols) {
-    return ((((row >> 5) * (cols >> 4) + (col >> 4)) * 2 + ((col >> 3) & 1)) * 32 + (row & 31)) * 8 + (col & 7);
-}
 // `tiled`: the transposed copies of this chunk go through LDS (see k_opt_adamw) and is not written here
 __device__ __forceinline__ void refresh_shadow(const g2048_opt_chunk &c, int i, float a, float b, float cc, float d, int n, bool tiled,
                                                uint16_t *stage) {
     const float vals[4] = {a, b, cc, d};
     const int64_t e = (int64_t)c.e0 + i;
     if (tiled) {
-        for (int q = 0; q < n; ++q) stage[i + q] = to_bf16(vals[q]);
+        for (int q = 0; q < n; ++q) stage[i + q] = (uint16_t)f2bf(vals[q]);
     }
     if (c.shadow_p) {  // fragment-packed copy: 4 consecutive columns of one row are 8 contiguous bytes there as well
         uint16_t *s = reinterpret_cast<uint16_t *>(c.shadow_p);
         const int64_t row = e / c.cols, col = e - row * c.cols;
         if (n == 4 && !(col & 3)) {
             *reinterpret_cast<uint2 *>(s + packed_off(row, col, c.cols)) =
-                make_uint2((uint32_t)to_bf16(a) | ((uint32_t)to_bf16(b) << 16), (uint32_t)to_bf16(cc) | ((uint32_t)to_bf16(d) << 16));
+                make_uint2(pack2(a, b), pack2(cc, d));
         } else {
             for (int q = 0; q < n; ++q) {
                 const int64_t eq = e + q, rq = eq / c.cols;
-                s[packed_off(rq, eq - rq * c.cols, c.cols)] = to_bf16(vals[q]);
+                s[packed_off(rq, eq - rq * c.cols, c.cols)] = (uint16_t)f2bf(vals[q]);
             }
         }
     }
@@ -132,23 +129,22 @@ __device__ __forceinline__ void refresh_shadow(const g2048_opt_chunk &c, int i, 
         uint16_t *t = reinterpret_cast<uint16_t *>(c.shadow_tp);
         for (int q = 0; q < n; ++q) {
             const int64_t eq = e + q, rq = eq / c.cols;
-            t[packed_off(eq - rq * c.cols, rq, c.rows)] = to_bf16(vals[q]);
+            t[packed_off(eq - rq * c.cols, rq, c.rows)] = (uint16_t)f2bf(vals[q]);
         }
     }
     if (c.shadow) {
         uint16_t *s = reinterpret_cast<uint16_t *>(c.shadow) + e;
         if (n == 4 && !((uintptr_t)s & 7)) {
-            *reinterpret_cast<uint2 *>(s) = make_uint2((uint32_t)to_bf16(a) | ((uint32_t)to_bf16(b) << 16),
-                                                       (uint32_t)to_bf16(cc) | ((uint32_t)to_bf16(d) << 16));
+            *reinterpret_cast<uint2 *>(s) = make_uint2(pack2(a, b), pack2(cc, d));
         } else {
-            for (int q = 0; q < n; ++q) s[q] = to_bf16(vals[q]);
+            for (int q = 0; q < n; ++q) s[q] = (uint16_t)f2bf(vals[q]);
         }
     }
     if (c.shadow_t && !tiled) {
         uint16_t *t = reinterpret_cast<uint16_t *>(c.shadow_t);
         for (int q = 0; q < n; ++q) {
             const int64_t eq = e + q, r = eq / c.cols, col = eq - r * c.cols;
-            t[col * c.rows + r] = to_bf16(vals[q]);
+            t[col * c.rows + r] = (uint16_t)f2bf(vals[q]);
         }
     }
 }
@@ -292,7 +288,7 @@ extern "C" int g2048_opt_step(const g2048_opt_chunk *chunks, int n_chunks, const
                               float *info, void *stream) {
     if (!chunks || n_chunks <= 0 || !grads || !exp_avg || !exp_avg_sq || !groups || n_groups <= 0 ||
         n_groups > G2048_OPT_MAX_GROUPS || !steps || n_steps <= 0 || !workspace || (scale && !growth_tracker) ||
-        (((uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)workspace) & 15))
+        !aligned16(grads, exp_avg, exp_avg_sq, workspace))
         return G2048_EINVAL;
     StepArgs A;
     for (int i = 0; i < G2048_OPT_MAX_GROUPS; ++i) A.groups[i] = groups[i < n_groups ? i : 0];
@@ -306,8 +302,7 @@ extern "C" int g2048_opt_step(const g2048_opt_chunk *chunks, int n_chunks, const
     F.steps = steps, F.growth_tracker = growth_tracker, F.info = info;
     hipLaunchKernelGGL(k_opt_adamw, dim3((unsigned)n_chunks), dim3(OPT_THREADS), 0, (hipStream_t)stream, chunks, n_chunks, grads,
                        exp_avg, exp_avg_sq, partial, derived, max_grad_norm, scale, F);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
+    return launch_status();
 }
 
 extern "C" int64_t g2048_opt_workspace_floats(int n_chunks) {

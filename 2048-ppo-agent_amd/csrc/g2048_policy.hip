@@ -45,16 +45,23 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <type_traits>
-
 #include "../../include/g2048.h"
+#include "g2048_host.h"
+#include "g2048_mfma.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// single names, not the namespace: this file has bias_tile / gemm_tile shapes of its own
+using g2048_mfma::bf16x4;
+using g2048_mfma::bf16x8;
+using g2048_mfma::f32x16;
+using g2048_mfma::f32x4;
+using g2048_mfma::mfma;
+using g2048_mfma::rowof;
+using g2048_mfma::sched_fence;
+using g2048_mfma::static_for;
+using namespace g2048_host;
+
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int D = 256, NH = 8, HD = 32, FF = 1024, SEQ = 17, NBOARD = 7, NTOK = 128, THREADS = 256;
@@ -67,8 +74,6 @@ constexpr int PO_LN1G = 0, PO_LN1B = D, PO_BQKV = 2 * D, PO_BO = 5 * D, PO_LN2G 
 constexpr int FFC = 64;               // feed-forward hidden units per pipeline stage
 constexpr int TILE = 32 * D * 2;      // bytes of a [32][256] (= [256][32]) bf16 tile: 16 KiB
 constexpr float SM_SCALE_LOG2E = 0.17677669529663687f * 1.4426950408889634f;  // 1/sqrt(32) * log2(e)
-
-__device__ __forceinline__ int rowof(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
 // swizzles: CPR = 16-byte chunks per row; chunk q of row r lives at q ^ swz(r), so that the 16 lanes of a
 // ds_read_b128 lane group (16 rows, distinct mod 16) always hit 16 different 16-byte bank slots
@@ -126,10 +131,6 @@ __device__ __forceinline__ bf16x8 load_p(const char *row, int ks, int h) {
     return *reinterpret_cast<const bf16x8 *>(row + 2 * (16 * ks + 8 * h));
 }
 
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
 // An accumulator tile X[row][col=lane] as the B operand of a product that sums over X's rows: registers
 // 8s..8s+7 are the fragment of k-step s, holding rows 16s + 8(j>>2) + 4h + (j&3).
 __device__ __forceinline__ void frag_from_acc(const f32x16 &x, bf16x8 out[2]) {
@@ -184,45 +185,15 @@ __device__ __forceinline__ void pipe_mfma() {
         if (i < NV && TRANS_PER) __builtin_amdgcn_sched_group_barrier(0x400, TRANS_PER, 0);
     }
 }
-// compile-time loop: f(integral_constant<int, I>) for I = I0..N-1, every index a constant (register arrays stay registers,
-// `if constexpr` on the step number prunes the body per step)
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-// nothing is scheduled across this point
-__device__ __forceinline__ void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
 
 // Diagnostic build only (-DG2048_STAMPS, tools/stamps_encoder.py; never compiled into the product library): cycle stamps
 // at phase boundaries, summed per phase in scalar registers and written to a table of their own at kernel exit.
 #ifdef G2048_STAMPS
 constexpr int N_STAMPS = 24;
 __device__ unsigned long long g_stamps[N_STAMPS];
-struct Stamps {
-    unsigned long long last, acc[N_STAMPS];
-    __device__ __forceinline__ void start() {
-        for (int i = 0; i < N_STAMPS; ++i) acc[i] = 0;
-        last = now();
-    }
-    __device__ __forceinline__ static unsigned long long now() {
-        unsigned long long t;
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-        __builtin_amdgcn_sched_barrier(0);
-        return t;
-    }
-    __device__ __forceinline__ void mark(int k) {
-        const unsigned long long t = now();
-        acc[k] += t - last;
-        last = t;
-    }
-    __device__ __forceinline__ void flush(int lane, int w) {
-        if (lane == 0 && w == 0 && blockIdx.x % 64 == 0)
-            for (int i = 0; i < N_STAMPS; ++i) atomicAdd(&g_stamps[i], acc[i]);
-    }
+struct StampSite {  // wave 0 of every 64th workgroup
+    __device__ __forceinline__ static bool on(int lane, int w) { return lane == 0 && w == 0 && blockIdx.x % 64 == 0; }
+    __device__ __forceinline__ static unsigned long long *table(int) { return g_stamps; }
 };
 #define STAMP(k) stamps.mark(k)
 #else
@@ -414,7 +385,7 @@ k_encoder_main(const uint8_t *__restrict__ boards, const float *__restrict__ tab
     };
 
 #ifdef G2048_STAMPS
-    Stamps stamps;
+    g2048_mfma::Stamps<N_STAMPS, StampSite> stamps;
     stamps.start();
 #endif
     // prologue: in_proj tiles of heads 0 and 1 of layer 0 (HEAD mode with a single layer: its K/V part reads them)
@@ -1029,16 +1000,13 @@ extern "C" int g2048_policy_encoder(const uint8_t *boards, const float *embed_ta
                                     float *features, int64_t B, void *workspace, void *stream) {
     if (!boards || !embed_table || !cls_token || !weights_bf16 || !params_f32 || !features || n_layers < 1 || B <= 0)
         return G2048_EINVAL;
-    if (((uintptr_t)weights_bf16 & 15) || ((uintptr_t)params_f32 & 15) || ((uintptr_t)embed_table & 15) ||
-        ((uintptr_t)cls_token & 15) || ((uintptr_t)features & 15) || ((uintptr_t)workspace & 15))
-        return G2048_EINVAL;
+    if (!aligned16(weights_bf16, params_f32, embed_table, cls_token, features, workspace)) return G2048_EINVAL;
     // the dynamic-LDS limit is a per-device function attribute: set on every call (no latch, no global state)
     const void *main_fn = workspace ? reinterpret_cast<const void *>(k_encoder_main<MODE_HEAD>)
                                     : reinterpret_cast<const void *>(k_encoder_main<MODE_FULL>);
-    if (hipFuncSetAttribute(main_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LdsMain)) != hipSuccess ||
-        (workspace && hipFuncSetAttribute(reinterpret_cast<const void *>(k_encoder_tail), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)sizeof(LdsTail)) != hipSuccess))
-        return -(1000 + (int)hipGetLastError());
+    if (const int rc = allow_dynamic_lds(main_fn, (int)sizeof(LdsMain))) return rc;
+    if (workspace)
+        if (const int rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_encoder_tail), (int)sizeof(LdsTail))) return rc;
     const __bf16 *wb = reinterpret_cast<const __bf16 *>(weights_bf16);
     const unsigned blocks = (unsigned)((B + NBOARD - 1) / NBOARD);
     if (!workspace) {
@@ -1053,8 +1021,7 @@ extern "C" int g2048_policy_encoder(const uint8_t *boards, const float *embed_ta
         hipLaunchKernelGGL(k_encoder_tail, dim3((unsigned)((B + NTOK - 1) / NTOK)), dim3(THREADS), sizeof(LdsTail),
                            (hipStream_t)stream, wb, params_f32, n_layers, features, B, ws_k, ws_v, ws_r);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
+    return launch_status();
 }
 
 extern "C" int g2048_policy_encoder_mean(const uint8_t *boards, const float *embed_table, const float *cls_token,
@@ -1062,16 +1029,11 @@ extern "C" int g2048_policy_encoder_mean(const uint8_t *boards, const float *emb
                                          int64_t B, void *stream) {
     if (!boards || !embed_table || !cls_token || !weights_bf16 || !params_f32 || !features || n_layers < 1 || B <= 0)
         return G2048_EINVAL;
-    if (((uintptr_t)weights_bf16 & 15) || ((uintptr_t)params_f32 & 15) || ((uintptr_t)embed_table & 15) ||
-        ((uintptr_t)cls_token & 15) || ((uintptr_t)features & 15))
-        return G2048_EINVAL;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_encoder_main<MODE_MEAN>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sizeof(LdsMain)) != hipSuccess)
-        return -(1000 + (int)hipGetLastError());
+    if (!aligned16(weights_bf16, params_f32, embed_table, cls_token, features)) return G2048_EINVAL;
+    if (const int rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_encoder_main<MODE_MEAN>), (int)sizeof(LdsMain))) return rc;
     const unsigned blocks = (unsigned)((B + NBOARD - 1) / NBOARD);
     hipLaunchKernelGGL(k_encoder_main<MODE_MEAN>, dim3(blocks), dim3(THREADS), sizeof(LdsMain), (hipStream_t)stream, boards,
                        embed_table, cls_token, reinterpret_cast<const __bf16 *>(weights_bf16), params_f32, n_layers, features, B,
                        (__bf16 *)nullptr, (__bf16 *)nullptr, (float *)nullptr);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
+    return launch_status();
 }

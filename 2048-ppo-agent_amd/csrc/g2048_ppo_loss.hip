@@ -12,6 +12,9 @@
 #include <stdint.h>
 
 #include "../../include/g2048.h"
+#include "g2048_host.h"
+
+using namespace g2048_host;
 
 namespace {
 
@@ -105,8 +108,7 @@ extern "C" int g2048_ppo_loss(const void *logits, int logits_bf16, const void *v
         return G2048_EINVAL;
     hipLaunchKernelGGL(k_ppo_loss, dim3(1), dim3(THREADS), 0, (hipStream_t)stream, logits, logits_bf16, values, values_bf16, actions,
                        mask_bits, old_logp, adv, ret, M, clip_eps, c_value, c_entropy, new_logp, sums, dlogits, dvalues, grad_scale, running);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
+    return launch_status();
 }
 
 // ---- minibatch gather ------------------------------------------------------------------------------------------------
@@ -140,11 +142,10 @@ extern "C" int g2048_gather_minibatch(const int64_t *idx, int64_t M, int64_t N, 
                                       uint8_t *o_boards, uint8_t *o_actions, uint8_t *o_masks, float *o_logp, float *o_adv,
                                       float *o_ret, void *stream) {
     if (!idx || !boards || !actions || !masks || !logp || !adv || !ret || !o_boards || !o_actions || !o_masks || !o_logp ||
-        !o_adv || !o_ret || M <= 0 || N <= 0 || (((uintptr_t)boards | (uintptr_t)o_boards) & 15))
+        !o_adv || !o_ret || M <= 0 || N <= 0 || !aligned16(boards, o_boards))
         return G2048_EINVAL;
     hipLaunchKernelGGL(k_gather_minibatch, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, idx, M, N,
                        (const uint4 *)boards, actions, masks, logp, adv, ret, (uint4 *)o_boards, o_actions, o_masks, o_logp, o_adv,
                        o_ret);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
+    return launch_status();
 }

@@ -11,8 +11,12 @@
 #include <stdint.h>
 
 #include "../../include/g2048.h"
+#include "g2048_bits.h"
+#include "g2048_host.h"
 
 namespace {
+
+using g2048_bits::bf2f;
 
 // Two workgroup shapes, chosen per job on the host:
 //   few parts (the split-K slices of a weight gradient, n up to 786 432): 256 threads x 4 columns, every thread walks the
@@ -28,8 +32,6 @@ struct JobTable {
     int32_t first_block[RJ_MAX + 1];
     int32_t n_jobs;
 };
-
-__device__ __forceinline__ float bf2f(uint32_t hi16) { return __uint_as_float(hi16 << 16); }
 
 constexpr int RJ_WIDE8_COLS = RJ_THREADS * 8;  // 2048 columns per workgroup
 // the all-vector case of the wide shape (host and device must agree: it decides the number of workgroups of the job)
@@ -161,6 +163,5 @@ extern "C" int g2048_reduce_jobs(const g2048_reduce_job *jobs, int n_jobs, void 
         for (int i = T.n_jobs; i <= RJ_MAX; ++i) T.first_block[i] = blocks;
         hipLaunchKernelGGL(k_reduce_jobs, dim3((unsigned)blocks), dim3(RJ_TX * RJ_TY), 0, (hipStream_t)stream, T);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
+    return g2048_host::launch_status();
 }

@@ -37,11 +37,13 @@
 #include <type_traits>
 
 #include "../../include/g2048.h"
+#include "g2048_host.h"
 #include "g2048_mfma.h"
 
 namespace {
 
 using namespace g2048_mfma;
+using namespace g2048_host;
 
 constexpr int RG_N = 256, RG_KC = 128, RG_THREADS = 512, RG_WAVES = 8;
 // NB = 32-token MFMA blocks per tile (3: tiles of <= 96 tokens, 5: <= 160).  Per NB: one K-chunk of the X tile in LDS (NB x 8 KB), 16-byte
@@ -52,7 +54,6 @@ template <int NB> struct RgShape {
     static_assert(PIECES * RG_THREADS == TT * (RG_KC / 8) && RPW % 2 == 0 && BATCH >= 1, "tile shape");
 };
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 enum { RG_FWD = 0, RG_BWD = 1 };
 
 struct RowGemmArgs {
@@ -79,12 +80,6 @@ struct RowGemmArgs {
     uint32_t thr, s0, s1;
     const uint64_t *seed_state;
 };
-
-__device__ __forceinline__ float bf2f(uint32_t hi16) { return __uint_as_float(hi16 << 16); }
-__device__ __forceinline__ uint32_t f2bf(float f) {
-    const __bf16 b = (__bf16)f;
-    return *reinterpret_cast<const uint16_t *>(&b);
-}
 
 // Sum over the 64 lanes, the same value in every lane: four DPP adds inside the 16-lane rows (quad permutes, half-row mirror, row
 // mirror), then the four row sums through scalar registers.  `__shfl_xor` compiles to ds_bpermute_b32: six LDS-crossbar round trips per
@@ -115,11 +110,7 @@ k_rowgemm(RowGemmArgs A) {
     float *const red = reinterpret_cast<float *>(smem + 2 * RG_STAGE);             // [8][3][256] (backward)
     float *const bias_l = reinterpret_cast<float *>(smem + 2 * RG_STAGE + RG_WAVES * 3 * RG_N * 4);
     uint32_t s0 = A.s0, s1 = A.s1;
-    if (A.seed_state) {  // the same mixing as g2048_layernorm.hip
-        const uint64_t s = *A.seed_state;
-        s0 ^= (uint32_t)s * 0x9E3779B1u;
-        s1 += (uint32_t)(s >> 32) * 0x85EBCA77u + (uint32_t)s;
-    }
+    mix_seed_state(A.seed_state, s0, s1);
     const int64_t n_tiles = (A.T + A.tpw - 1) / A.tpw;
     if (tid < RG_N) bias_l[tid] = (MODE == RG_FWD && A.bias) ? A.bias[tid] : 0.f;
 
@@ -424,11 +415,6 @@ k_rowgemm(RowGemmArgs A) {
     }
 }
 
-inline int rg_done() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
-}
-
 // Tile size: ONE tile per workgroup when T allows it (136 tokens = 8 boards at T = 34 816: 256 workgroups, one round on 256 CUs), because
 // every tile streams the whole weight through its CU once - 512 KB from L2 at K = 1024 - and five token blocks per weight fragment
 // amortise that better than three.  Measured (linear2 + add + LayerNorm at T = 34 816, cold operands): one 136-token tile per workgroup
@@ -451,9 +437,9 @@ template <int MODE, int NB, int NCH>
 int rg_launch3(RowGemmArgs &A, unsigned grid, hipStream_t stream) {
     const void *fn = reinterpret_cast<const void *>(k_rowgemm<MODE, NB, NCH>);
     constexpr int lds = RgShape<NB>::LDS;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -(1000 + (int)hipGetLastError());
+    if (const int rc = allow_dynamic_lds(fn, lds)) return rc;
     hipLaunchKernelGGL((k_rowgemm<MODE, NB, NCH>), dim3(grid), dim3(RG_THREADS), lds, stream, A);
-    return rg_done();
+    return launch_status();
 }
 template <int MODE, int NB>
 int rg_launch2(RowGemmArgs &A, unsigned grid, hipStream_t stream) {
@@ -475,7 +461,7 @@ int rg_launch(RowGemmArgs &A, hipStream_t stream) {
 }
 
 inline bool rg_gemm_ok(const void *x, int64_t ldx, const void *w, int64_t T, int K) {
-    return x && w && T > 0 && K >= 256 && K % 256 == 0 && K <= 1024 && ldx >= K && !(ldx & 7) && !(((uintptr_t)x | (uintptr_t)w) & 15) &&
+    return x && w && T > 0 && K >= 256 && K % 256 == 0 && K <= 1024 && ldx >= K && !(ldx & 7) && aligned16(x, w) &&
            (int64_t)160 * ldx * 2 < (1ll << 31);
 }
 
@@ -494,7 +480,7 @@ extern "C" int g2048_linear_add_ln_fwd(const void *u, int64_t ldu, const void *w
                                        float *rstd, int64_t T, float eps, float p_drop, uint64_t seed, const uint64_t *seed_state,
                                        void *stream) {
     if (!rg_gemm_ok(u, ldu, w_packed, T, K) || !x || !gamma || !beta || !x_new || !h || !mean || !rstd || !(p_drop >= 0.f && p_drop < 1.f) ||
-        (x_row_stride & 3) || (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)x_new | (uintptr_t)bias) & 15) ||
+        (x_row_stride & 3) || !aligned16(x, gamma, beta, x_new, bias) ||
         ((uintptr_t)h & 7))
         return G2048_EINVAL;
     RowGemmArgs A{};
@@ -515,7 +501,7 @@ extern "C" int g2048_linear_add_ln_bwd(const void *dy, int64_t lddy, const void 
         return G2048_EINVAL;
     if (!rg_gemm_ok(dy, lddy, wt_packed, T, K) || !x_norm || !mean || !rstd || !gamma || !dx || !partial || g_x_period < 1 ||
         !(p_drop >= 0.f && p_drop < 1.f) || (x_row_stride & 3) ||
-        (((uintptr_t)x_norm | (uintptr_t)g_x | (uintptr_t)gamma | (uintptr_t)dx) & 15) || ((uintptr_t)da & 7) || ((uintptr_t)partial & 3))
+        !aligned16(x_norm, g_x, gamma, dx) || ((uintptr_t)da & 7) || ((uintptr_t)partial & 3))
         return G2048_EINVAL;
     RowGemmArgs A{};
     A.x = (const __bf16 *)dy; A.ldx = lddy; A.w = (const __bf16 *)wt_packed; A.T = T; A.K = K;

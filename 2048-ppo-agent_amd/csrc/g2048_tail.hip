@@ -26,14 +26,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <type_traits>
-
 #include "../../include/g2048.h"
+#include "g2048_host.h"
 #include "g2048_mfma.h"
 
 namespace {
 
 using namespace g2048_mfma;
+using namespace g2048_host;
 
 constexpr int D = 256, FF = 1024, HID = 512, TB = 32, THREADS = 256, FC = 128;
 constexpr int S256 = 2 * 256 + 16, S512 = 2 * 512 + 16, S128 = 2 * 128 + 16;  // LDS row strides in bytes (+16: bank spread)
@@ -734,12 +734,6 @@ k_dweight_t(DwTable T) {
     }
 }
 
-inline int done() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
-}
-inline bool mis16(const void *p) { return !p || ((uintptr_t)p & 15); }
-
 }  // namespace
 
 extern "C" int g2048_cls_tail_fwd(const void *o, const float *x_cls, int64_t x_row_stride, const g2048_tail_weights *W,
@@ -750,16 +744,14 @@ extern "C" int g2048_cls_tail_fwd(const void *o, const float *x_cls, int64_t x_r
                           W->ab2, W->cb1, W->cb2, W->ln_g, W->ln_b, S->x_mid, S->masks, S->oT, S->h2T, S->uT, S->featsT, S->a1T,
                           S->a2T, S->c1T, S->c2T, logits};
     for (const void *p : ptrs)
-        if (mis16(p)) return G2048_EINVAL;
+        if (!p || !aligned16(p)) return G2048_EINVAL;
     if (!values || !S->mean || !S->rstd || ((uintptr_t)values & 3)) return G2048_EINVAL;
     const int64_t blocks = (M + TB - 1) / TB;
     if (S->ld < blocks * TB || (S->ld & 7)) return G2048_EINVAL;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_tail_fwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sizeof(TailLds)) != hipSuccess)
-        return -(1000 + (int)hipGetLastError());
+    if (const int rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_tail_fwd), (int)sizeof(TailLds))) return rc;
     hipLaunchKernelGGL(k_tail_fwd, dim3((unsigned)blocks, 2), dim3(THREADS), sizeof(TailLds), (hipStream_t)stream, (const __bf16 *)o, x_cls,
                        x_row_stride, *W, *S, logits, values, M, eps, p_drop, seed, seed_state);
-    return done();
+    return launch_status();
 }
 
 extern "C" int g2048_cls_tail_bwd(const float *dlogits, const float *dvalues, const g2048_tail_weights_t *WT,
@@ -770,16 +762,14 @@ extern "C" int g2048_cls_tail_bwd(const float *dlogits, const float *dvalues, co
                           S->masks, G->daoT, G->dzT, G->df2T, G->da1T, G->da2T, G->dlT, G->dc1T, G->dc2T, G->dvT, G->ln_partial, d_o,
                           dx_cls};
     for (const void *p : ptrs)
-        if (mis16(p)) return G2048_EINVAL;
+        if (!p || !aligned16(p)) return G2048_EINVAL;
     if (!dvalues || !S->mean || !S->rstd || ((uintptr_t)dvalues & 3)) return G2048_EINVAL;
     const int64_t blocks = (M + TB - 1) / TB;
     if (S->ld < blocks * TB || (S->ld & 7)) return G2048_EINVAL;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_tail_bwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sizeof(TailLds)) != hipSuccess)
-        return -(1000 + (int)hipGetLastError());
+    if (const int rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_tail_bwd), (int)sizeof(TailLds))) return rc;
     hipLaunchKernelGGL(k_tail_bwd, dim3((unsigned)blocks), dim3(THREADS), sizeof(TailLds), (hipStream_t)stream, dlogits, dvalues, *WT, *S, *G,
                        (__bf16 *)d_o, dx_cls, M, p_drop, seed, seed_state);
-    return done();
+    return launch_status();
 }
 
 extern "C" int g2048_dweight_t(const g2048_dw_job *jobs, int n_jobs, int64_t ld, int64_t m, int slices, void *stream) {
@@ -793,7 +783,7 @@ extern "C" int g2048_dweight_t(const g2048_dw_job *jobs, int n_jobs, int64_t ld,
     int items = 0;
     for (int j = 0; j < n_jobs; ++j) {
         const g2048_dw_job &J = jobs[j];
-        if (mis16(J.dyT) || mis16(J.xT) || mis16(J.dw) || J.N <= 0 || J.K <= 0 || (J.N & 31) || (J.K & 63) || ((uintptr_t)J.db & 3))
+        if (!J.dyT || !J.xT || !J.dw || !aligned16(J.dyT, J.xT, J.dw) || J.N <= 0 || J.K <= 0 || (J.N & 31) || (J.K & 63) || ((uintptr_t)J.db & 3))
             return G2048_EINVAL;
         T.jobs[j] = J;
         T.first_item[j] = items;
@@ -803,5 +793,5 @@ extern "C" int g2048_dweight_t(const g2048_dw_job *jobs, int n_jobs, int64_t ld,
     const int per_block = THREADS / 64;
     hipLaunchKernelGGL(k_dweight_t, dim3((unsigned)(((items + per_block - 1) / per_block) * slices)), dim3(THREADS), 0, (hipStream_t)stream,
                        T);
-    return done();
+    return launch_status();
 }
