@@ -23,16 +23,6 @@ struct StepKeyTable {
     u32 k[G2048_MAX_FUSED_STEPS][4];  // act sub-key, step sub-key per lock-step (wave-uniform -> SGPRs)
 };
 
-__device__ __forceinline__ Board load_board(const uint8_t *p, int64_t i) {
-    const uint4 v = reinterpret_cast<const uint4 *>(p)[i];
-    Board b;
-    b.r[0] = v.x; b.r[1] = v.y; b.r[2] = v.z; b.r[3] = v.w;
-    return b;
-}
-__device__ __forceinline__ void store_board(uint8_t *p, int64_t i, const Board &b) {
-    reinterpret_cast<uint4 *>(p)[i] = make_uint4(b.r[0], b.r[1], b.r[2], b.r[3]);
-}
-
 // ---------------------------------------------------------------------------------------- RNG
 template <int MODE>
 __global__ void __launch_bounds__(kBlock) k_split(u32 k0, u32 k1, u32 *out, int64_t n) {

@@ -246,6 +246,19 @@ G_DEV u32 board_move(Board &bd, u32 a) {
     return score;
 }
 
+#if defined(__HIPCC__) && !defined(G2048_HOST_TEST)
+// board i of a packed u8[.][16] array <-> registers: one 16-byte vector access per lane, 1 KiB per wave-instruction
+__device__ __forceinline__ Board load_board(const uint8_t *p, int64_t i) {
+    const uint4 v = reinterpret_cast<const uint4 *>(p)[i];
+    Board b;
+    b.r[0] = v.x; b.r[1] = v.y; b.r[2] = v.z; b.r[3] = v.w;
+    return b;
+}
+__device__ __forceinline__ void store_board(uint8_t *p, int64_t i, const Board &b) {
+    reinterpret_cast<uint4 *>(p)[i] = make_uint4(b.r[0], b.r[1], b.r[2], b.r[3]);
+}
+#endif
+
 // bit 7 of every byte that holds a tile (valid for cell values <= 0x80)
 G_DEV u32 tile_bits(u32 row) { return (row + 0x7F7F7F7Fu) & 0x80808080u; }
 

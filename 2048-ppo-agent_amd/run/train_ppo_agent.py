@@ -44,6 +44,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default=os.path.join(os.path.dirname(HERE), "configs", "train_ppo_agent.yaml"))
     ap.add_argument("--eval-episodes", type=int, default=0, help="greedy masked evaluation after training")
+    ap.add_argument("--eval-lookahead", type=int, default=0,
+                    help="1: the evaluation plays one-ply expectimax over the critic instead of the actor's argmax")
     ap.add_argument("overrides", nargs="*")
     args = ap.parse_args()
     cfg = load_config(args.config, args.overrides)
@@ -90,7 +92,7 @@ def main():
         tail = trainer.episode_rewards[-100:]
         logger.info("Final mean episode reward (last 100 episodes): %.2f", sum(tail) / len(tail))
     if args.eval_episodes and trainer.rank == 0:
-        print(json.dumps(evaluate_agent(agent, device, args.eval_episodes)))
+        print(json.dumps(evaluate_agent(agent, device, args.eval_episodes, lookahead=args.eval_lookahead, gamma=t["gamma"])))
     if world > 1:
         dist.destroy_process_group()
 

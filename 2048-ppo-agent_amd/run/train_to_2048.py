@@ -47,6 +47,9 @@ def main():
     ap.add_argument("--stop-at-2048", action="store_true", help="stop training at the first 2048 tile")
     ap.add_argument("--out", default=None)
     ap.add_argument("--seed", type=int, default=0, help="seed of the weights, the environments and the minibatch order")
+    ap.add_argument("--eval-lookahead", type=int, default=0,
+                    help="1: every evaluation point also plays one-ply expectimax over the critic on the same seeds (key 'lookahead')")
+    ap.add_argument("--save-agent", default=None, help="write the final agent's state_dict here (tools/probe_lookahead.py reads it)")
     a = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -64,15 +67,30 @@ def main():
 
     def evaluate(minutes):
         ev = evaluate_agent(agent, dev, 1000) if rank == 0 else None
+        if ev is not None and a.eval_lookahead:
+            # the same 1000 episodes' seeds, the same weights; the greedy figures keep their keys (earlier result files stay comparable)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            la = evaluate_agent(agent, dev, 1000, lookahead=a.eval_lookahead, gamma=TRAINER["gamma"])
+            torch.cuda.synchronize()
+            la.update(depth=a.eval_lookahead, gamma=TRAINER["gamma"], eval_seconds=round(time.perf_counter() - t0, 1))
+            ev["lookahead"] = la
         if world > 1:
             dist.barrier()
         if ev is not None:
             ev.update(train_minutes=round(minutes, 2), timesteps=tr.total_timesteps)
             print(f"eval @ {minutes:.2f} min / {tr.total_timesteps} steps: mean max tile {ev['mean_max_tile']:.1f}  {ev['percent']}",
                   flush=True)
+            if "lookahead" in ev:
+                la = ev["lookahead"]
+                print(f"  lookahead {la['depth']}: mean max tile {la['mean_max_tile']:.1f}  {la['percent']}  ({la['eval_seconds']} s)", flush=True)
+            if a.out:  # the evaluation points so far, should the run be cut short (the full result replaces this file at the end)
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)) or ".", exist_ok=True)
+                json.dump({"partial": True, "evals": evals + [ev]}, open(a.out, "w"), indent=1)
         return ev
 
-    evals = [evaluate(0.0)]
+    evals = []
+    evals.append(evaluate(0.0))
     train_s, it, first_2048, log = 0.0, 0, None, []
     next_eval = a.minutes / (a.evals + 1)
     while train_s / 60 < a.minutes:
@@ -108,6 +126,9 @@ def main():
             evals.append(evaluate(train_s / 60))
             next_eval += a.minutes / (a.evals + 1)
     evals.append(evaluate(train_s / 60))
+    if rank == 0 and a.save_agent:
+        os.makedirs(os.path.dirname(os.path.abspath(a.save_agent)) or ".", exist_ok=True)
+        torch.save(agent.state_dict(), a.save_agent)
     if rank == 0:
         res = {"config": "BASELINE.json configs[4] protocol" + ("" if world * 131072 == a.envs else
                          f" at {a.envs} envs on {world} GPU(s) (the 1 M-env / 8-GPU size needs an 8-GPU node)"),

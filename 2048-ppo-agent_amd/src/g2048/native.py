@@ -48,6 +48,9 @@ SIGNATURES = {
     "g2048_policy_encoder_workspace_bytes": [_i64],
     "g2048_policy_encoder": [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp],
     "g2048_policy_encoder_mean": [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp],
+    "g2048_lookahead_expand": [_vp, _i64, _vp, _vp, _vp, _vp],
+    "g2048_lookahead_children": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "g2048_lookahead_reduce": [_vp, _vp, _vp, _vp, _vp, _dbl, _i64, _i64, _vp, _vp],
     "g2048_attn_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, C.c_float,
                        C.c_float, C.c_uint64, _vp, _vp],
     "g2048_attn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -345,6 +348,39 @@ def policy_encoder_mean(boards, embed_table, cls_token, weights_bf16, params_f32
         _dev(cls_token, f32, 256, "cls_token"), _dev(weights_bf16, torch.bfloat16, n_layers * 786432, "weights_bf16"),
         _dev(params_f32, f32, n_layers * 3328, "params_f32"), n_layers, _dev(features, f32, 256 * B, "features"), B,
         _stream()), "g2048_policy_encoder_mean")
+
+
+def lookahead_expand(boards, after, reward, nchild):
+    """boards u8 [B,16] -> after u8 [B,4,16], reward f32 [B,4], nchild i32 [B,4] (0 for an illegal move)."""
+    B = boards.numel() // 16
+    _check(load().g2048_lookahead_expand(_dev(boards, u8, 16 * B, "boards"), B, _dev(after, u8, 64 * B, "after"),
+                                         _dev(reward, f32, 4 * B, "reward"), _dev(nchild, i32, 4 * B, "nchild"), _stream()),
+           "g2048_lookahead_expand")
+
+
+def lookahead_children(after, nchild, offset, N: int, children, terminal):
+    """The N = nchild.sum() children in (b, a, cell, tile) order: children u8 [>= N,16], terminal u8 [>= N].  ``offset`` is the
+    exclusive prefix sum of ``nchild``; rows past N are left alone."""
+    B = nchild.numel() // 4
+    N = int(N)
+    if N < 0:
+        raise NativeError("lookahead_children: N must not be negative")
+    _check(load().g2048_lookahead_children(_dev(after, u8, 64 * B, "after"), _dev(nchild, i32, 4 * B, "nchild"),
+                                           _dev(offset, i32, 4 * B, "offset"), B, N,
+                                           _dev(children, u8, 16 * N, "children"), _dev(terminal, u8, N, "terminal"), _stream()),
+           "g2048_lookahead_children")
+
+
+def lookahead_reduce(reward, nchild, offset, values, terminal, gamma: float, N: int, q):
+    """q f32 [B,4] = reward + gamma * E_spawn[V(child)], V = 0 at terminal children; 0 where nchild == 0."""
+    B = nchild.numel() // 4
+    N = int(N)
+    if N < 0:
+        raise NativeError("lookahead_reduce: N must not be negative")
+    _check(load().g2048_lookahead_reduce(_dev(reward, f32, 4 * B, "reward"), _dev(nchild, i32, 4 * B, "nchild"),
+                                         _dev(offset, i32, 4 * B, "offset"), _dev(values, f32, N, "values"),
+                                         _dev(terminal, u8, N, "terminal"), float(gamma), B, N, _dev(q, f32, 4 * B, "q"), _stream()),
+           "g2048_lookahead_reduce")
 
 
 def attn_fwd(q_ptr: int, k_ptr: int, v_ptr: int, o, lse, B: int, H: int, Sq: int, strides, scale: float, p_drop: float,

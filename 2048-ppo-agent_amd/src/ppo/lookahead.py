@@ -1,0 +1,107 @@
+"""One-ply expectimax play: the critic looked up behind every possible spawn, on the device (no reference counterpart).
+
+    Q(s, a) = r(s, a) + gamma * E_{s' ~ spawn(after(s, a))} [ V(s') ],     V(terminal s') = 0
+
+The env model is the engine's own (``board_move`` / ``board_legal``), the spawn law is the env's (uniform over the empty
+cells of the afterstate, tile 2 with p = 0.9, tile 4 with p = 0.1), so the expectation is exact; only V is learned.  Per
+lock-step: ``g2048_lookahead_expand`` (four afterstates per board) -> ``torch.cumsum`` over the 4 B child counts, whose total
+is read back once (the children have to be sized for the forward) -> ``g2048_lookahead_children`` -> the agent's value
+forward on the children, in chunks of ``max_children`` rows -> ``g2048_lookahead_reduce``.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from ..actions import _common as C
+from ..env_definitions import BOARD_FLAT_DIM, OBS_DIM
+from ..g2048 import native as nv
+from .torch_action_wrapper import TorchActionFunction
+
+
+class LookaheadActionFunction(TorchActionFunction):
+    """``TorchActionFunction`` whose "logits" are the one-ply expectimax values ``Q(s, .)`` of the agent's critic.
+
+    ``policy_fn(boards, masks)`` returns ``(q f32 [B, 4], v f32 [B])`` with ``v = max over the legal actions of q`` (0 where
+    there is none).  ``use_mask=True, sample_actions=False`` are forced, so the engine (``g2048_policy_step``) takes the
+    masked argmax of ``q`` exactly as it does for actor logits; the env, its key stream and the trajectory format are
+    untouched.  The recorded ``log_prob`` is therefore the log-softmax of ``q`` at the chosen action: NOT a policy
+    probability (``q`` is in score units), so such trajectories are for evaluation, not for a PPO update.
+
+    ``gamma``: discount on the children's values (default: the trainer's 0.99).  ``depth``: only 1.  ``max_children``: rows per
+    value-forward call (the forward of a 65 536-board batch would otherwise allocate activations for millions of rows).
+    The value forward is the agent's existing one: ``FusedPolicy.__call__`` for a bf16 default-shape PPOAgent of either
+    reduction, ``TorchActionFunction._forward`` otherwise; the children's logits are discarded.  A function kept across
+    optimiser steps sees the new weights (the fused pack is refreshed when stale, the module forward reads the parameters).
+    """
+
+    def __init__(self, agent, gamma: float = 0.99, depth: int = 1, max_children: int = 1 << 18,
+                 device: torch.device = torch.device("cpu"), amp_dtype: Optional[torch.dtype] = None, sync_every: int = 8,
+                 rng_mode=None, use_fused: Optional[bool] = None):
+        if depth != 1:
+            raise ValueError(f"LookaheadActionFunction: only depth=1 is implemented, got depth={depth!r}")
+        if int(max_children) <= 0:
+            raise ValueError("max_children must be a positive number of rows")
+        super().__init__(agent, use_mask=True, sample_actions=False, device=device, amp_dtype=amp_dtype,
+                         sync_every=sync_every, rng_mode=rng_mode, use_fused=use_fused)
+        self.gamma = float(gamma)
+        self.depth = 1
+        self.max_children = int(max_children)
+        self.last_children = 0  # N of the latest policy_fn call (probes and tests read it; no extra synchronisation)
+
+    def _values(self, rows: torch.Tensor) -> torch.Tensor:
+        """The agent's critic on packed boards u8 [n, 16] -> f32 [n]."""
+        agent_dev = next(self.agent.parameters()).device
+        if self._fused is not None and rows.device == agent_dev:
+            return self._fused(rows)[1]
+        return self._forward(rows, agent_dev)[1]
+
+    @torch.no_grad()
+    def policy_fn(self, boards: torch.Tensor, masks: torch.Tensor = None):
+        """boards u8 [B, 16], masks unused (legality comes out of the expansion) -> (q f32 [B, 4], v f32 [B])."""
+        boards = boards.contiguous()
+        B, dev = boards.shape[0], boards.device
+        after = torch.empty((B, 4, 16), dtype=torch.uint8, device=dev)
+        reward = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        nchild = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        nv.lookahead_expand(boards, after, reward, nchild)
+        incl = torch.cumsum(nchild.view(-1), 0, dtype=torch.int32)
+        offset = (incl - nchild.view(-1)).view(B, 4)
+        N = self.last_children = int(incl[-1].item())  # the one host read of the lock-step
+        children = torch.empty((N, 16), dtype=torch.uint8, device=dev)
+        terminal = torch.empty(N, dtype=torch.uint8, device=dev)
+        values = torch.empty(N, dtype=torch.float32, device=dev)
+        nv.lookahead_children(after, nchild, offset, N, children, terminal)
+        for c0 in range(0, N, self.max_children):
+            c1 = min(N, c0 + self.max_children)
+            values[c0:c1] = self._values(children[c0:c1]).to(torch.float32).reshape(-1)
+        q = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        nv.lookahead_reduce(reward, nchild, offset, values, terminal, self.gamma, N, q)
+        legal = nchild > 0
+        v = torch.where(legal, q, torch.full_like(q, float("-inf"))).max(dim=1).values
+        return q, torch.where(legal.any(dim=1), v, torch.zeros_like(v))
+
+    policy_fn.needs_masks = False
+
+    @torch.no_grad()
+    def __call__(self, rng_key, obs, mask):
+        """Un-batched plug-in protocol ``(rng_key[2], obs[4,4,31], mask[4]) -> (action, log_prob, value)``; leading batch
+        dimensions are accepted.  The one-hot observation is decoded to a packed board and goes down ``policy_fn``."""
+        obs_t = torch.as_tensor(np.asarray(obs.cpu() if isinstance(obs, torch.Tensor) else obs))
+        batched = obs_t.ndim > 3
+        dev = C.device()
+        boards = obs_t.reshape(-1, BOARD_FLAT_DIM, OBS_DIM).to(torch.float32).argmax(dim=-1).to(torch.uint8).to(dev)
+        q, values = self.policy_fn(boards, None)
+        bits = C.mask_to_bits(mask)
+        keys = C.keys_tensor(rng_key)
+        n = bits.numel()
+        actions = torch.empty(n, dtype=torch.int32, device=dev)
+        logp = torch.empty(n, dtype=torch.float32, device=dev)
+        mode = C.default_rng_mode() if self.rng_mode is None else self.rng_mode
+        nv.act_logits(keys, q.contiguous(), bits, True, False, actions, logp, mode)
+        a, lp, v = actions.cpu().numpy(), logp.cpu().numpy(), values.cpu().numpy()
+        if batched:
+            return a, lp, v
+        return np.int32(a[0]), np.float32(lp[0]), np.float32(v[0])

@@ -42,12 +42,20 @@ def evaluate_max_tile(act_fn: Callable, num_episodes: int = 1000, seed: int = 42
     }
 
 
-def evaluate_agent(agent, device, num_episodes: int = 1000, seed: int = 42, rng_mode=None) -> Dict:
-    """Greedy, masked evaluation of a PPO agent (run/viz_ppo_agent.py:267-300)."""
+def evaluate_agent(agent, device, num_episodes: int = 1000, seed: int = 42, rng_mode=None, lookahead: int = 0,
+                   gamma: float = 0.99) -> Dict:
+    """Greedy, masked evaluation of a PPO agent (run/viz_ppo_agent.py:267-300).  ``lookahead=1``: the same protocol (same
+    seeds, same env and key stream) played by one-ply expectimax over the agent's critic with discount ``gamma``
+    (``LookaheadActionFunction``) instead of the actor's argmax; ``lookahead=0`` is the reference's evaluation."""
     from ..ppo.torch_action_wrapper import TorchActionFunction
 
     was_training = agent.training
-    fn = TorchActionFunction(agent, use_mask=True, sample_actions=False, device=device)
+    if lookahead:
+        from ..ppo.lookahead import LookaheadActionFunction
+
+        fn = LookaheadActionFunction(agent, gamma=gamma, depth=lookahead, device=device)
+    else:
+        fn = TorchActionFunction(agent, use_mask=True, sample_actions=False, device=device)
     try:
         return evaluate_max_tile(fn, num_episodes, seed, rng_mode=rng_mode, device=device)
     finally:

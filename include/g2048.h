@@ -194,6 +194,36 @@ int g2048_policy_encoder_mean(const uint8_t *boards, const float *embed_table, c
                               const void *weights_bf16, const float *params_f32, int n_layers, float *features,
                               int64_t B, void *stream);
 
+/* ---- one-ply expectimax over the critic (no reference counterpart: the reference only ever asks the actor) -----------
+ * Q(s, a) = r(s, a) + gamma * E_{s' ~ spawn(after(s, a))} V(s'), V(terminal s') = 0, with the spawn law of the env (uniform
+ * over the empty cells of the afterstate, tile 2 with p = 0.9, tile 4 with p = 0.1).  Three kernels around the caller's
+ * value forward: expand -> (exclusive prefix sum of nchild, by the caller) -> children -> V(children) -> reduce.
+ * Pairs (b, a) are indexed p = 4 * b + a; offset i32[B][4] is the exclusive prefix sum of nchild in that order and N its
+ * total (host: the caller reads it back once to size the children and the forward). */
+
+/* after u8[B][4][16] = the board slid in direction a (the input board where the move is illegal); reward f32[B][4] = the
+ * merge score g2048_step returns for that move (0 where illegal); nchild i32[B][4] = 2 * (empty cells of the afterstate)
+ * where the move is legal, 0 where not.  One lane per board; 16 B read, 96 B written per board.
+ * G2048_EINVAL: a null pointer, B outside 1 .. 2^24, a pointer that is not 16-byte aligned. */
+int g2048_lookahead_expand(const uint8_t *boards, int64_t B, uint8_t *after, float *reward, int32_t *nchild, void *stream);
+
+/* children u8[N][16], terminal u8[N]: the children of pair p occupy rows offset[p] .. offset[p] + nchild[p], ordered by
+ * empty cell in ascending (row-major) cell index and within a cell tile 2 (log2 = 1) first, tile 4 (log2 = 2) second;
+ * terminal[i] = 1 iff child i has no legal move.  One lane per child, one 16-byte store each; rows at or past N are not
+ * touched, and a lane whose offset / nchild / afterstate disagree writes nothing.  N = 0 launches nothing.
+ * G2048_EINVAL: a null pointer (children / terminal may be null when N = 0), B outside 1 .. 2^24, N < 0 or N > 120 * B,
+ * after / children not 16-byte aligned, nchild / offset not 4-byte aligned. */
+int g2048_lookahead_children(const uint8_t *after, const int32_t *nchild, const int32_t *offset, int64_t B, int64_t N,
+                             uint8_t *children, uint8_t *terminal, void *stream);
+
+/* q f32[B][4] = reward + (float)gamma * ((sum over the n_e = nchild / 2 cells j, ascending, of 0.9f * v[2j] + 0.1f * v[2j+1])
+ * / n_e), v = values f32[N] of the pair's children with 0 where terminal (a select: a terminal child's value is never
+ * read into the sum); every product and sum rounded to f32 on its own.  q = 0 where nchild = 0.  One lane per (b, a).
+ * G2048_EINVAL: a null pointer (values / terminal may be null when N = 0), B outside 1 .. 2^24, N < 0 or N > 120 * B,
+ * values not 8-byte aligned, terminal not 2-byte aligned, the others not 4-byte aligned. */
+int g2048_lookahead_reduce(const float *reward, const int32_t *nchild, const int32_t *offset, const float *values,
+                           const uint8_t *terminal, double gamma, int64_t B, int64_t N, float *q, void *stream);
+
 /* ---- policy network (update): attention for 17-token sequences ------------------------------------- */
 
 /* softmax(q k^T * scale) v with attention dropout, head_dim 32, Sk = 17 keys, Sq = 17 queries (or 1: the CLS row

@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""Cost of one lock-step of one-ply expectimax play next to a greedy lock-step, on one GPU.
+
+    python tools/probe_lookahead.py [--agent state_dict.pt] [--boards 100 65536] [--repeats 7] [--out result.json]
+
+For each batch size: boards that the agent's own greedy play visits (half an episode's worth of lock-steps into a rollout, so the
+fill of the boards is that of real play), then, with HIP events after a warm-up, the time of
+  greedy     TorchActionFunction.policy_fn (bf16, the fused encoder for a default-shape agent)
+  lookahead  LookaheadActionFunction.policy_fn on the same boards (same precision, same encoder on every child)
+and of the parts of the lookahead lock-step: the three new kernels, the prefix sum with its host read, the value forward.
+Every figure is the median of ``--repeats`` timed repeats with the min and max next to it.  Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, "..", "2048-ppo-agent_amd"))
+
+import torch  # noqa: E402
+
+from src.g2048 import native as nv  # noqa: E402
+from src.ppo import LookaheadActionFunction, PPOAgent, TorchActionFunction  # noqa: E402
+from src.runs import BatchRunner  # noqa: E402
+
+MODEL = dict(observation_dim=31, action_dim=4, hidden_dim=512, d_model=256, nhead=8, num_layers=4, dim_feedforward=1024,
+             dropout=0.1, reduction="cls")
+
+
+def timed(fn, repeats, warmup=3):
+    """-> {"median_ms", "min_ms", "max_ms"} of ``repeats`` event-timed calls after ``warmup`` untimed ones."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
+
+
+def mid_game_boards(agent, B, dev, steps=96):
+    """The boards after ``steps`` greedy lock-steps of a fresh batch (boards that ended earlier stay in, as they do in a rollout)."""
+    fn = TorchActionFunction(agent, use_mask=True, sample_actions=False, device=dev, amp_dtype=torch.bfloat16)
+    eng = BatchRunner(init_seed=7, act_fn=fn, device=dev)._engine
+    traj = eng.rollout_policy_fixed(B, steps, fn.policy_fn, use_mask=True, sample=False)
+    return traj.boards[steps - 1].contiguous()
+
+
+def probe(agent, B, dev, repeats):
+    boards = mid_game_boards(agent, B, dev)
+    greedy = TorchActionFunction(agent, use_mask=True, sample_actions=False, device=dev, amp_dtype=torch.bfloat16)
+    look = LookaheadActionFunction(agent, device=dev, amp_dtype=torch.bfloat16)
+    res = {"boards": B, "fused_encoder": look._fused is not None,
+           "greedy": timed(lambda: greedy.policy_fn(boards, None), repeats),
+           "lookahead": timed(lambda: look.policy_fn(boards, None), repeats)}
+    N = look.last_children
+    res["children"] = N
+    res["children_per_board"] = round(N / B, 2)
+    # the parts, on the tensors of one expansion
+    after = torch.empty((B, 4, 16), dtype=torch.uint8, device=dev)
+    reward = torch.empty((B, 4), dtype=torch.float32, device=dev)
+    nchild = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    nv.lookahead_expand(boards, after, reward, nchild)
+    incl = torch.cumsum(nchild.view(-1), 0, dtype=torch.int32)
+    offset = (incl - nchild.view(-1)).view(B, 4)
+    children = torch.empty((N, 16), dtype=torch.uint8, device=dev)
+    terminal = torch.empty(N, dtype=torch.uint8, device=dev)
+    values = torch.empty(N, dtype=torch.float32, device=dev)
+    q = torch.empty((B, 4), dtype=torch.float32, device=dev)
+    nv.lookahead_children(after, nchild, offset, N, children, terminal)
+
+    def scan():
+        c = torch.cumsum(nchild.view(-1), 0, dtype=torch.int32)
+        (c - nchild.view(-1)).view(B, 4)
+        return int(c[-1].item())
+
+    def forward():
+        for c0 in range(0, N, look.max_children):
+            values[c0:c0 + look.max_children] = look._values(children[c0:c0 + look.max_children])
+
+    parts = {"expand": timed(lambda: nv.lookahead_expand(boards, after, reward, nchild), repeats),
+             "scan_and_host_read": timed(scan, repeats),
+             "children": timed(lambda: nv.lookahead_children(after, nchild, offset, N, children, terminal), repeats),
+             "value_forward": timed(forward, repeats),
+             "reduce": timed(lambda: nv.lookahead_reduce(reward, nchild, offset, values, terminal, look.gamma, N, q), repeats)}
+    res["parts"] = parts
+    kernels = sum(parts[k]["median_ms"] for k in ("expand", "children", "reduce"))
+    res["new_kernels_ms"] = round(kernels, 4)
+    res["new_kernels_share_of_lockstep"] = round(kernels / res["lookahead"]["median_ms"], 4)
+    res["lookahead_over_greedy"] = round(res["lookahead"]["median_ms"] / res["greedy"]["median_ms"], 2)
+    # expand 16 r + 96 w; children 64 + 32 r + 17 w per child; reduce 48 r + 5 r per child + 16 w
+    res["bytes_per_board_new_kernels"] = round(272 + 22 * N / B, 1)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--agent", default=None, help="state_dict of a default-shape PPOAgent (run/train_to_2048.py --save-agent); default: fresh weights")
+    ap.add_argument("--boards", type=int, nargs="+", default=[100, 65536])
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("probe_lookahead.py measures on the GPU; none is visible")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    torch.manual_seed(a.seed)
+    agent = PPOAgent(**MODEL)
+    if a.agent:
+        agent.load_state_dict(torch.load(a.agent, map_location="cpu"))
+    agent = agent.to(dev).eval()
+    res = {"agent": os.path.basename(a.agent) if a.agent else "fresh weights", "precision": "bfloat16", "repeats": a.repeats,
+           "timer": "HIP events around one policy_fn call, 3 warm-up calls, median [min, max]",
+           "runs": [probe(agent, B, dev, a.repeats) for B in a.boards]}
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)) or ".", exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
