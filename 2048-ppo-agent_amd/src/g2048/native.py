@@ -96,6 +96,9 @@ SIGNATURES = {
     "g2048_dweight_jobs": [_vp, _i32, _vp],
     "g2048_opt_workspace_floats": [_i32],
     "g2048_opt_step": [_vp, _i32, _vp, _vp, _vp, _vp, _i32, C.c_float, _vp, _i32, _vp, _vp, C.c_float, C.c_float, _i32, _vp, _vp, _vp],
+    "g2048_lamb_workspace_floats": [_i32],
+    "g2048_lamb_step": [_vp, _i32, _vp, _vp, _vp, _vp, _i32, C.c_float, C.c_float, _vp, _i32, _vp, _vp, C.c_float, C.c_float, _i32, _vp,
+                        _vp, _vp],
 }
 
 _lib = None
@@ -817,6 +820,34 @@ def opt_step(table, n_chunks: int, grads, exp_avg, exp_avg_sq, groups, max_grad_
         _dev(growth_tracker, torch.int32, 1, "growth_tracker", optional=True), float(growth), float(backoff),
         int(growth_interval), _dev(workspace, f32, None, "workspace"), _dev(info, f32, 2, "info", optional=True), _stream()),
         "g2048_opt_step")
+
+
+class LambGroup(C.Structure):  # g2048_lamb_group
+    _fields_ = [("lr", _dbl), ("beta1", _dbl), ("beta2", _dbl), ("beta3", _dbl), ("eps", _dbl), ("weight_decay", _dbl),
+                ("bias_correction", C.c_int32), ("adapt", C.c_int32), ("trust_clip", C.c_int32), ("reserved", C.c_int32)]
+
+
+def lamb_workspace(n_chunks: int, device) -> torch.Tensor:
+    """Zeroed workspace for g2048_lamb_step (three partial sums per chunk, the step's flags, the per-group constants)."""
+    return torch.zeros(load().g2048_lamb_workspace_floats(n_chunks), dtype=f32, device=device)
+
+
+def lamb_step(table, n_chunks: int, grads, exp_avg, exp_avg_sq, groups, max_grad_norm: float, lamb_max_grad_norm, steps, scale,
+              growth_tracker, growth: float, backoff: float, growth_interval: int, workspace, info=None):
+    """Clip + LAMB (+ GradScaler unscale / skip / update when ``scale`` is given) for every chunk of ``table`` (an
+    ``opt_chunk_table``); ``groups``: list of (lr, beta1, beta2, beta3, eps, weight_decay, bias_correction, adapt, trust_clip);
+    ``lamb_max_grad_norm``: Lamb's own clip threshold, None or 0 for none."""
+    if len(groups) > OPT_MAX_GROUPS:
+        raise NativeError(f"lamb_step: {len(groups)} parameter groups, at most {OPT_MAX_GROUPS} are supported")
+    g = (LambGroup * len(groups))(*[LambGroup(*map(float, t[:6]), *(int(bool(x)) for x in t[6:9]), 0) for t in groups])
+    n = grads.numel()
+    _check(load().g2048_lamb_step(
+        table.data_ptr(), n_chunks, _dev(grads, f32, None, "grads"), _dev(exp_avg, f32, n, "exp_avg"),
+        _dev(exp_avg_sq, f32, n, "exp_avg_sq"), C.cast(g, _vp), len(groups), float(max_grad_norm if max_grad_norm else 0.0),
+        float(lamb_max_grad_norm if lamb_max_grad_norm else 0.0), _dev(steps, f32, 1, "steps"), steps.numel(),
+        _dev(scale, f32, 1, "scale", optional=True), _dev(growth_tracker, torch.int32, 1, "growth_tracker", optional=True),
+        float(growth), float(backoff), int(growth_interval), _dev(workspace, f32, None, "workspace"),
+        _dev(info, f32, 2, "info", optional=True), _stream()), "g2048_lamb_step")
 
 
 def gather_minibatch(idx, boards, actions, masks, logp, adv, ret, out=None):

@@ -22,7 +22,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 from torch.amp import GradScaler, autocast
 
-from ..optim.flat_step import FlatAdamWStep
+from ..optim.flat_step import flat_step_for
 from ..optim import configure_bert_optimizers
 from ..runs.batch_runner import BatchRunner
 from .data_loader import DeviceBatches, PPODataset
@@ -310,12 +310,12 @@ class PPOTrainer:
         # armed only around a forward+backward whose gradients ARE all-reduced afterwards (update_policy's eager minibatch, a capture
         # that includes the collectives): a stray backward (graph warm-up, a test calling _loss_backward) must not start one
         self._early_armed = False
-        # clip + AdamW + GradScaler bookkeeping as two launches over flat buffers (g2048_opt_step) for the reference's
-        # default optimiser on the device; anything else (LAMB, Adam, CPU) takes the PyTorch calls of the reference
+        # clip + optimiser + GradScaler bookkeeping as two (AdamW: g2048_opt_step) or three (LAMB: g2048_lamb_step) launches over
+        # flat buffers on the device; anything else (Adam, CPU) takes the PyTorch calls of the reference, and so does everything
+        # with G2048_FLAT_OPT=0 (the A/B switch)
         self._flat_step = None
-        if os.environ.get("G2048_FLAT_OPT", "1").strip().lower() not in ("0", "false", "no", "off") \
-                and FlatAdamWStep.supports(self.optimizer, self.device):
-            self._flat_step = FlatAdamWStep(self.optimizer, self.device, first=self._early_params)
+        if os.environ.get("G2048_FLAT_OPT", "1").strip().lower() not in ("0", "false", "no", "off"):
+            self._flat_step = flat_step_for(self.optimizer, self.device, first=self._early_params)
         if self.world > 1 or self._flat_step is not None:
             self._bind_flat_grads()
         if self.world > 1:
@@ -831,6 +831,8 @@ class PPOTrainer:
         """torch.save of the reference's checkpoint dict (same keys; rank 0 only in a multi-GPU run)."""
         if self.rank != 0:
             return
+        if self._flat_step is not None:
+            self._flat_step.sync_step_counts()  # step counts that live on the device while the flat step runs (LAMB)
         ckpt = {
             "agent_state_dict": self.agent.state_dict(), "optimizer_state_dict": self.optimizer.state_dict(),
             "total_timesteps": self.total_timesteps, "total_epochs": self.total_epochs,
@@ -851,6 +853,8 @@ class PPOTrainer:
             raise ValueError(f"Checkpoint missing required keys: {missing}")
         self.agent.load_state_dict(ckpt["agent_state_dict"])
         if load_optimizer:
+            if self._flat_step is not None:
+                self._flat_step.sync_step_counts()  # (a load that fails keeps the live state: its step count must be current too)
             try:
                 self.optimizer.load_state_dict(ckpt["optimizer_state_dict"])
             except Exception as e:  # keep training with a fresh optimizer, as the reference does

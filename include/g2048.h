@@ -521,6 +521,30 @@ int g2048_opt_step(const g2048_opt_chunk *chunks, int n_chunks, const float *gra
                    int32_t *growth_tracker, float growth, float backoff, int growth_interval, float *workspace,
                    float *info, void *stream);
 
+/* The same step with the reference's LAMB optimiser (src/optim/lamb.py:106-209 inside the update loop of
+ * src/ppo/ppo_trainer.py:413-434: scaler.unscale_(opt); clip_grad_norm_(params, max_grad_norm); scaler.step(Lamb);
+ * scaler.update()), in three launches over the same chunk table, flat buffers, scaler scalars and info as g2048_opt_step:
+ *   g = grad * inv_scale;  norm = ||g|| over all chunks;  c1 = min(1, max_grad_norm / (norm + 1e-6)) (max_grad_norm <= 0: 1);
+ *   c2 = max(1, norm * c1 / lamb_max_grad_norm) (Lamb's own global clip, optimizer.defaults["max_grad_norm"]; <= 0: none.  The
+ *   reference takes that norm again from the clipped elements; norm * c1 differs from it by rounding only and saves a pass);
+ *   g' = g * c1 / c2, applied as grad * (float)(inv_scale * c1 / c2) with the factor formed in f64 from the f32 sum of squares and
+ *   rounded once (two roundings per element where the reference's three passes have five);  m = beta1 * m + beta3 * g';  v = beta2 * v + (1 - beta2) * g'^2;
+ *   u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + weight_decay * p   (bc1, bc2 in f64 from the step count; 1 without bias_correction);
+ *   per TENSOR, when weight_decay != 0 or adapt: r = ||p|| / ||u|| if both are > 0, else 1; min(r, 1) with trust_clip; else r = 1;
+ *   p -= lr * r * u, the chunk's bf16 shadows rewritten.
+ * The chunks of one tensor must be adjacent and in ascending e0 order, with rows * cols = the tensor's element count (what
+ * opt_chunk_table writes): the per-tensor norms are summed over them in that order.  beta3 = 1 - beta1 (grad_averaging) or 1.
+ * steps: device f32 [n_steps], every entry +1 per non-skipped call; the bias corrections use steps[0] (Lamb keeps one count per
+ * group, FlatLambStep one for all).  Skipping, scale / growth_tracker, info, argument checks and error codes: as g2048_opt_step.
+ * workspace: g2048_lamb_workspace_floats(n_chunks) floats. */
+typedef struct { double lr, beta1, beta2, beta3, eps, weight_decay;
+                 int32_t bias_correction, adapt, trust_clip, reserved; } g2048_lamb_group;
+int64_t g2048_lamb_workspace_floats(int n_chunks);
+int g2048_lamb_step(const g2048_opt_chunk *chunks, int n_chunks, const float *grads, float *exp_avg, float *exp_avg_sq,
+                    const g2048_lamb_group *groups, int n_groups, float max_grad_norm, float lamb_max_grad_norm,
+                    float *steps, int n_steps, float *scale, int32_t *growth_tracker, float growth, float backoff,
+                    int growth_interval, float *workspace, float *info, void *stream);
+
 /* ---- policy network (update): the 2048-row tail as two kernels -------------------------------------------------- */
 
 /* Everything after the last encoder layer's attention works on ONE row per board (the "cls" reduction reads only the CLS row
