@@ -281,6 +281,7 @@ def test_mfma_attention_equals_scalar_attention(dev, monkeypatch):
     """The 17-token attention on MFMA tiles (default) vs the scalar kernels (G2048_ATTN_SCALAR=1) on the same inputs and the
     SAME dropout seed: both use the element index (pair * 17 + query) * 32 + key for the mask, so outputs, log-sum-exps and
     gradients agree to bf16 rounding and either forward can be paired with either backward."""
+    from attention_ref import lse_bound
     from src.g2048 import native as nv
 
     H, hd, S = 8, 32, 17
@@ -305,7 +306,11 @@ def test_mfma_attention_equals_scalar_attention(dev, monkeypatch):
                 res[impl] = (o, lse, dqkv)
             (o1, l1, g1), (o2, l2, g2) = res["mfma"], res["scalar"]
             assert rel(o1, o2) < 6e-3, (B, p_drop, rel(o1, o2))
-            assert torch.allclose(l1, l2, rtol=1e-5, atol=2e-2), (l1 - l2).abs().max()  # scores from bf16 MFMA vs f32 FMAs
+            # each kernel's lse lies within the derived f32 bound of the float64 value (attention_ref.lse_bound, held with a margin of
+            # 12 x on the MI355X by tests/test_gpu_attention.py): two kernels differ by at most twice it (3e-5 here; was atol = 2e-2)
+            q4, k4 = (qkv.view(B, S, 3, H, hd)[:, :, i].transpose(1, 2).cpu() for i in (0, 1))
+            bound = 2.0 * lse_bound(q4, k4, hd ** -0.5)
+            assert ((l1 - l2).abs().cpu().double() <= bound).all(), ((l1 - l2).abs().max(), bound.max())
             assert rel(g1, g2) < 8e-3, (B, p_drop, rel(g1, g2))
             if p_drop > 0:  # the same entries are dropped: zeros of the attention-weighted sums cannot be compared directly,
                 # but an output row with every key dropped is exactly zero in both
