@@ -31,6 +31,22 @@ __device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
+// v_mfma_f32_32x32x16_f16: the same operand and accumulator maps as the bf16 form (csrc/g2048_f32split.hip)
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ f32x16 mfma_f16(f16x8 a, f16x8 b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+// two-way fp16 split of s * v (s a power of two): hi = f16(s v), lo = f16(s v - hi); the subtraction is exact in f32
+__device__ __forceinline__ void split_f16(const float v[8], float s, f16x8 &hi, f16x8 &lo) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float sv = s * v[j];
+        const _Float16 t = (_Float16)sv;
+        hi[j] = t;
+        lo[j] = (_Float16)(sv - (float)t);
+    }
+}
+
 // compile-time loop: f(integral_constant<int, I>) for I = I0..N-1, every index a constant (register arrays stay registers,
 // `if constexpr` on the step number prunes the body per step)
 template <int I, int N, class Fn>

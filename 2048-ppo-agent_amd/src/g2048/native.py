@@ -48,6 +48,10 @@ SIGNATURES = {
     "g2048_policy_encoder_workspace_bytes": [_i64],
     "g2048_policy_encoder": [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp],
     "g2048_policy_encoder_mean": [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp],
+    "g2048_f32split_pack": [_vp, _i32, _i32, C.c_float, _vp, _vp],
+    "g2048_f32split_gemm": [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp],
+    "g2048_attn_fwd_f32": [_vp, _vp, _i64, _i32, C.c_float, _vp],
+    "g2048_embed_ln_f32": [_vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _i64, _vp],
     "g2048_lookahead_expand": [_vp, _i64, _vp, _vp, _vp, _vp],
     "g2048_lookahead_children": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
     "g2048_lookahead_reduce": [_vp, _vp, _vp, _vp, _vp, _dbl, _i64, _i64, _vp, _vp],
@@ -351,6 +355,52 @@ def policy_encoder_mean(boards, embed_table, cls_token, weights_bf16, params_f32
         _dev(cls_token, f32, 256, "cls_token"), _dev(weights_bf16, torch.bfloat16, n_layers * 786432, "weights_bf16"),
         _dev(params_f32, f32, n_layers * 3328, "params_f32"), n_layers, _dev(features, f32, 256 * B, "features"), B,
         _stream()), "g2048_policy_encoder_mean")
+
+
+F32SPLIT_BIAS, F32SPLIT_BIAS_RELU, F32SPLIT_ADD_LN, F32SPLIT_ADD = 0, 1, 2, 3
+
+
+def f32split_pack(w, scale: float, packed):
+    """w f32 [N, K] -> ``packed`` (float16, 2 N K elements): hi / lo planes of ``w * scale`` in fragment order (``g2048_f32split_pack``)."""
+    N, K = w.shape
+    _check(load().g2048_f32split_pack(_dev(w, f32, N * K, "w"), N, K, float(scale), _dev(packed, torch.float16, 2 * N * K, "packed"),
+                                      _stream()), "g2048_f32split_pack")
+
+
+def _rows(t, dtype, cols: int, name: str):
+    """(data_ptr, row stride) of a 2-D device tensor with unit column stride."""
+    if t is None or not t.is_cuda or t.dtype != dtype or t.dim() != 2 or t.shape[1] < cols or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise NativeError(f"{name}: expected a 2-D {dtype} HIP tensor with >= {cols} unit-stride columns")
+    return t.data_ptr(), t.stride(0)
+
+
+def f32split_gemm(x, w_packed, bias, y, K: int, N: int, epilogue: int, sx: float, sw: float, resid=None, gamma=None, beta=None, h=None,
+                  eps: float = 1e-5, T=None):
+    """y[:T] = epilogue(x[:T] @ W^T + bias) as a split-fp16 product (``g2048_f32split_gemm``); x, y 2-D f32 (row strides free)."""
+    T = x.shape[0] if T is None else int(T)
+    (xp, ldx), (yp, ldy) = _rows(x, f32, K, "x"), _rows(y, f32, N, "y")
+    if x.shape[0] < T or y.shape[0] < T:
+        raise NativeError("f32split_gemm: fewer than T rows")
+    _check(load().g2048_f32split_gemm(
+        xp, ldx, _dev(w_packed, torch.float16, 2 * N * K, "w_packed"), _dev(bias, f32, N, "bias"), yp, ldy,
+        _dev(resid, f32, T * 256, "resid", optional=True), _dev(gamma, f32, 256, "gamma", optional=True),
+        _dev(beta, f32, 256, "beta", optional=True), _dev(h, f32, T * 256, "h", optional=True), T, K, N, epilogue, float(sx), float(sw),
+        float(eps), _stream()), "g2048_f32split_gemm")
+
+
+def attn_fwd_f32(qkv, o, B: int, H: int, scale: float):
+    """qkv f32 [B, 17, 96 H] -> o f32 [B, 17, 32 H] (``g2048_attn_fwd_f32``)."""
+    _check(load().g2048_attn_fwd_f32(_dev(qkv, f32, B * 17 * 96 * H, "qkv"), _dev(o, f32, B * 17 * 32 * H, "o"), B, H, float(scale),
+                                     _stream()), "g2048_attn_fwd_f32")
+
+
+def embed_ln_f32(boards, table, cls, gamma, beta, eps: float, x0, h):
+    """boards u8 [B, 16] -> x0, h = LayerNorm(x0) f32 [B, 17, 256] (``g2048_embed_ln_f32``)."""
+    B = boards.numel() // 16
+    _check(load().g2048_embed_ln_f32(_dev(boards, u8, 16 * B, "boards"), _dev(table, f32, 16 * 31 * 256, "table"), _dev(cls, f32, 256, "cls"),
+                                     _dev(gamma, f32, 256, "gamma"), _dev(beta, f32, 256, "beta"), float(eps),
+                                     _dev(x0, f32, B * 17 * 256, "x0"), _dev(h, f32, B * 17 * 256, "h"), B, _stream()),
+           "g2048_embed_ln_f32")
 
 
 def lookahead_expand(boards, after, reward, nchild):

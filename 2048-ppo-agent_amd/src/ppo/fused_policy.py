@@ -1,4 +1,5 @@
-"""Rollout-time policy forward through the fused MFMA encoder kernel (csrc/g2048_policy.hip).
+"""Rollout-time policy forward through the fused MFMA encoder kernel (csrc/g2048_policy.hip), and (``FusedPolicyF32``, at the end)
+the fp32 rollout forward through the split-fp16 kernels (csrc/g2048_f32split.hip).
 
 Usable when the agent is a PPOAgent of the reference's default shape (d_model 256, 8 heads, feed-forward 1024) on a
 HIP device and the rollout is asked to run in bf16.  The encoder (embedding -> 17-token Transformer -> CLS feature, or
@@ -7,6 +8,7 @@ on the [B, 256] features.  Same numerics class as torch.autocast(bf16): bf16 GEM
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -194,3 +196,142 @@ class FusedPolicy:
                         x = torch.relu_(x)
             outs.append(x)
         return outs[0].float(), outs[1].float().reshape(-1)
+
+
+# ------------------------------------------------------------------------------------------------ fp32 rollout, split-fp16 kernels
+F16_TOP = 2.0 ** 15  # |scale * operand| never exceeds this (fp16's largest finite value is 65504)
+_BOUND_SLACK = 1.0 + 2.0 ** -8  # the bounds below are exact-arithmetic statements; the f32 forward rounds
+
+
+def pow2_scale(bound: float) -> float:
+    """The largest power of two s with s * bound * slack <= 2^15 (bound 0 or non-finite: 1)."""
+    if not (bound > 0.0 and math.isfinite(bound)):
+        return 1.0
+    return 2.0 ** math.floor(math.log2(F16_TOP / (bound * _BOUND_SLACK)))
+
+
+@torch.no_grad()
+def f32_split_scales(agent):
+    """Per encoder layer the eight power-of-two scales of the split-fp16 products (csrc/g2048_f32split.hip), as a dict of floats:
+    ``h1 a h2 f`` for the operands of in_proj / out_proj / linear1 / linear2 and ``wqkv wo w1 w2`` for their weights.
+
+    Weight scales come from max |w|.  Activation scales come from bounds that hold for EVERY input, so no operand can overflow and
+    there is no fallback path: a LayerNorm output is z * g + b with |z_n| <= ||z||_2 <= 16 (256 features), hence
+    |h_n| <= 16 |g_n| + |b_n|; a Linear behind it obeys |W_n . h + c_n| <= 16 ||W_n * g||_2 + |W_n . b + c_n| (Cauchy-Schwarz), which
+    bounds the values (so their convex combinations, the attention output) and the ReLU'd hidden activations.  Typical operands sit
+    a factor 4 .. 16 under these bounds, i.e. around 2^11 .. 2^13 after scaling, 14 binades above the 2^-3 where the lo half
+    would leave fp16's normal range."""
+    rows = []
+    for l in agent.transformer.encoder.layers:
+        f = lambda x: x.detach().double()
+        g1, b1, g2, b2 = f(l.norm1.weight), f(l.norm1.bias), f(l.norm2.weight), f(l.norm2.bias)
+        wqkv, bqkv = f(l.self_attn.in_proj_weight), f(l.self_attn.in_proj_bias)
+        D = g1.numel()
+        wv, bv = wqkv[2 * D:], bqkv[2 * D:]
+        w1, c1 = f(l.linear1.weight), f(l.linear1.bias)
+        rows.append(torch.stack([
+            (16 * g1.abs() + b1.abs()).max(),
+            (16 * (wv * g1).norm(dim=1) + (wv @ b1 + bv).abs()).max(),
+            (16 * g2.abs() + b2.abs()).max(),
+            (16 * (w1 * g2).norm(dim=1) + (w1 @ b2 + c1).abs()).max(),
+            wqkv.abs().max(), f(l.self_attn.out_proj.weight).abs().max(), w1.abs().max(), f(l.linear2.weight).abs().max()]))
+    vals = torch.stack(rows).cpu().tolist()  # one device -> host copy for the whole agent
+    return [dict(zip(("h1", "a", "h2", "f", "wqkv", "wo", "w1", "w2"), map(pow2_scale, v))) for v in vals]
+
+
+class FusedPolicyF32:
+    """The fp32 rollout forward of a default-shape PPOAgent on the split-fp16 kernels: embedding + LayerNorm, then per layer
+    in_proj GEMM, f32 attention, out_proj GEMM (+ residual + norm2), linear1 GEMM (+ ReLU), linear2 GEMM (+ residual + the next
+    layer's norm1); every activation between kernels f32, no LayerNorm folding.  The reduction and the two heads (2 % of the FLOPs)
+    are the module's own f32 operators.  Same ``refresh_if_stale()`` contract as ``FusedPolicy``."""
+
+    CHUNK_BOARDS = 8192  # boards per pass: bounds the f32 activation workspace at 10 KB per token
+
+    def __init__(self, agent):
+        if not (supports(agent) or supports_mean(agent)):
+            raise ValueError("agent shape not supported by the split-fp16 forward")
+        self.agent = agent
+        self.mean = agent.reduction == "mean"
+        self._key = None
+        self._ws = None
+        self.refresh()
+
+    _params_key = FusedPolicy._params_key
+    refresh_if_stale = FusedPolicy.refresh_if_stale
+
+    @torch.no_grad()
+    def refresh(self):
+        self._key = self._params_key()
+        a, t = self.agent, self.agent.transformer
+        dev = next(a.parameters()).device
+        emb = a.input_embedding.weight.t().float()  # [31, 256]
+        pe = t.positional_encoding.flat_table().float()  # [16, 256]
+        self.table = (emb[None, :, :] + pe[:, None, :]).contiguous()  # [16, 31, 256]: the module's embedding + position, one f32 add
+        self.cls = t.cls_token.detach().float().reshape(256).contiguous()
+        self.scales = f32_split_scales(a)
+        self.layers = []
+        for l, s in zip(t.encoder.layers, self.scales):
+            f = lambda x: x.detach().float().contiguous()
+            ws = {}
+            for key, w in (("wqkv", l.self_attn.in_proj_weight), ("wo", l.self_attn.out_proj.weight), ("w1", l.linear1.weight),
+                           ("w2", l.linear2.weight)):
+                ws[key] = torch.empty(2 * w.numel(), dtype=torch.float16, device=dev)
+                nv.f32split_pack(f(w), s[key], ws[key])
+            # biases and LayerNorm parameters: one blob, every vector at a multiple of 256 floats (16-byte aligned whatever the
+            # parameters' own storage is)
+            vecs = [l.self_attn.in_proj_bias, l.self_attn.out_proj.bias, l.linear1.bias, l.linear2.bias, l.norm1.weight, l.norm1.bias,
+                    l.norm2.weight, l.norm2.bias]
+            blob = torch.cat([f(v).reshape(-1) for v in vecs])
+            offs = [0, 768, 1024, 2048, 2304, 2560, 2816, 3072, 3328]
+            ws.update(zip(("bqkv", "bo", "b1", "b2", "g1", "be1", "g2", "be2"), (blob[offs[i]:offs[i + 1]] for i in range(8))))
+            ws["eps1"], ws["eps2"] = float(l.norm1.eps), float(l.norm2.eps)
+            self.layers.append(ws)
+
+    def _workspace(self, B: int, device):
+        ws = self._ws
+        if ws is None or ws[0].shape[0] < 17 * B or ws[0].device != device:
+            T = 17 * B
+            e = lambda n: torch.empty((T, n), dtype=torch.float32, device=device)
+            ws = self._ws = (e(256), e(256), e(768), e(256), e(1024))
+        return ws
+
+    @torch.no_grad()
+    def encode(self, boards: torch.Tensor) -> torch.Tensor:
+        """boards u8 [B <= CHUNK_BOARDS, 16] -> the encoder output f32 [B, 17, 256] (a view of the workspace)."""
+        boards = boards.contiguous()
+        B = boards.shape[0]
+        T = 17 * B
+        x, h, qkv, att, ff = self._workspace(B, boards.device)
+        L = self.layers
+        nv.embed_ln_f32(boards, self.table, self.cls, L[0]["g1"], L[0]["be1"], L[0]["eps1"], x, h)
+        for i, (w, s) in enumerate(zip(L, self.scales)):
+            nv.f32split_gemm(h, w["wqkv"], w["bqkv"], qkv, 256, 768, nv.F32SPLIT_BIAS, s["h1"], s["wqkv"], T=T)
+            nv.attn_fwd_f32(qkv, att, B, 8, 1.0 / math.sqrt(32.0))
+            nv.f32split_gemm(att, w["wo"], w["bo"], x, 256, 256, nv.F32SPLIT_ADD_LN, s["a"], s["wo"], resid=x, gamma=w["g2"], beta=w["be2"],
+                             h=h, eps=w["eps2"], T=T)
+            nv.f32split_gemm(h, w["w1"], w["b1"], ff, 256, 1024, nv.F32SPLIT_BIAS_RELU, s["h2"], s["w1"], T=T)
+            if i + 1 < len(L):
+                nxt = L[i + 1]
+                nv.f32split_gemm(ff, w["w2"], w["b2"], x, 1024, 256, nv.F32SPLIT_ADD_LN, s["f"], s["w2"], resid=x, gamma=nxt["g1"],
+                                 beta=nxt["be1"], h=h, eps=nxt["eps1"], T=T)
+            else:
+                nv.f32split_gemm(ff, w["w2"], w["b2"], x, 1024, 256, nv.F32SPLIT_ADD, s["f"], s["w2"], resid=x, T=T)
+        return x[:T].view(B, 17, 256)
+
+    @torch.no_grad()
+    def features(self, boards: torch.Tensor) -> torch.Tensor:
+        """boards u8 [B, 16] -> CLS (or board-token mean) features f32 [B, 256]."""
+        if boards.shape[0] == 0:
+            return torch.empty((0, 256), dtype=torch.float32, device=boards.device)
+        outs = []
+        for b0 in range(0, boards.shape[0], self.CHUNK_BOARDS):
+            x = self.encode(boards[b0:b0 + self.CHUNK_BOARDS])
+            outs.append(x[:, 1:, :].mean(dim=1) if self.mean else x[:, 0, :].clone())
+        return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+    @torch.no_grad()
+    def __call__(self, boards: torch.Tensor):
+        """boards u8 [B, 16] -> (logits f32 [B, 4] (unmasked), values f32 [B])."""
+        self.refresh_if_stale()
+        feats = self.features(boards)
+        return self.agent.actor(feats).float(), self.agent.critic(feats).float().reshape(-1)

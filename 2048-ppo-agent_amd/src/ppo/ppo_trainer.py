@@ -219,8 +219,11 @@ class PPOTrainer:
                  rollout_amp: Optional[bool] = None,
                  log_dir: str = "logs", use_hip_graph: Optional[bool] = None, rollout_mode: Optional[str] = None,
                  rollout_horizon: Optional[int] = None, allreduce_dtype: Optional[str] = None,
-                 allreduce_in_graph: Optional[bool] = None):
+                 allreduce_in_graph: Optional[bool] = None, fp32_native: Optional[bool] = None):
         self.agent = agent.to(device)
+        # fp32 rollouts (rollout_amp False) of a default-shape PPOAgent through the split-fp16 kernels (fused_policy.FusedPolicyF32);
+        # None: G2048_ROLLOUT_FP32_NATIVE decides (TorchActionFunction), default off
+        self.fp32_native = fp32_native
         self._acc_in_kernel, self._acc5 = True, None  # see _running_sums
         self.batch_runner = batch_runner
         self.rollout_buffer = rollout_buffer
@@ -497,7 +500,7 @@ class PPOTrainer:
         self.rollout_buffer.reset()
         self.agent.eval()
         act = TorchActionFunction(self.agent, use_mask=self.use_action_mask, device=self.device,
-                                  amp_dtype=self.amp_dtype if self.rollout_amp else None,
+                                  amp_dtype=self.amp_dtype if self.rollout_amp else None, fp32_native=self.fp32_native,
                                   graph_cache=self._rollout_graphs if getattr(self.agent, "rollout_graph_ok", False) else None)
         self.batch_runner.act_fn = act
         local_b, env0, total = self._shard(batch_size)

@@ -7,6 +7,7 @@ env step in ``g2048_policy_step`` / available stand-alone as ``g2048_act_logits`
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import numpy as np
@@ -18,6 +19,14 @@ from ..g2048 import native as nv
 from .capture import capture as capture_graph
 
 
+def resolve_fp32_native(fp32_native=None, environ=None) -> bool:
+    """An explicit argument wins; else G2048_ROLLOUT_FP32_NATIVE=1/true/yes/on (parsed like G2048_ROLLOUT_FP32); default off."""
+    if fp32_native is not None:
+        return bool(fp32_native)
+    environ = os.environ if environ is None else environ
+    return environ.get("G2048_ROLLOUT_FP32_NATIVE", "0").strip().lower() in ("1", "true", "yes", "on")
+
+
 class TorchActionFunction:
     """Wrap an actor-critic ``agent`` as an ``act_fn`` plug-in for BatchRunner.
 
@@ -26,13 +35,16 @@ class TorchActionFunction:
     ``amp_dtype`` runs the rollout forward under autocast (the reference rolls out in fp32) -- for bfloat16 and a
     PPOAgent of the reference's default shape ("cls" or "mean" reduction) the encoder then runs in the fused MFMA kernel unless
     ``use_fused=False``; ``sync_every`` is how many lock-steps are enqueued between polls of the device-side
-    live-env counter.
+    live-env counter; ``fp32_native`` sends an fp32 rollout (``amp_dtype`` None) of such a PPOAgent on a HIP device through the
+    split-fp16 kernels (``fused_policy.FusedPolicyF32``: f32-grade results on the f16 matrix cores) - ``None`` asks
+    G2048_ROLLOUT_FP32_NATIVE (default off); anywhere else the switch does nothing and the module forward runs.
     Side effect as in the reference: ``agent`` is moved to ``device`` and put in eval mode.
     """
 
     def __init__(self, agent, use_mask: bool = False, sample_actions: bool = True,
                  device: torch.device = torch.device("cpu"), amp_dtype: Optional[torch.dtype] = None,
-                 sync_every: int = 8, rng_mode=None, use_fused: Optional[bool] = None, graph_cache: Optional[dict] = None):
+                 sync_every: int = 8, rng_mode=None, use_fused: Optional[bool] = None, graph_cache: Optional[dict] = None,
+                 fp32_native: Optional[bool] = None):
         self.agent = agent.to(device).eval()
         self.use_mask = use_mask
         self.sample_actions = sample_actions
@@ -47,6 +59,13 @@ class TorchActionFunction:
 
             if fused_policy.supports(self.agent) or fused_policy.supports_mean(self.agent):
                 self._fused = fused_policy.FusedPolicy(self.agent)
+        # fp32 rollouts of the same agents: the split-fp16 forward (csrc/g2048_f32split.hip), opt-in
+        self.fp32_native = resolve_fp32_native(fp32_native)
+        if amp_dtype is None and self.fp32_native:
+            from . import fused_policy
+
+            if fused_policy.supports(self.agent) or fused_policy.supports_mean(self.agent):
+                self._fused = fused_policy.FusedPolicyF32(self.agent)
         # a cheap policy (the MLP of BASELINE configs[1]: ~15 launches of microseconds per lock-step) is launch-bound in eager
         # mode: with a ``graph_cache`` (owned by the caller, it outlives this object) the forward over ALL boards of the batch is
         # replayed from a hipGraph and the engine skips the live-board compaction (``compact``), whose gathers cost more than

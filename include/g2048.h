@@ -194,6 +194,46 @@ int g2048_policy_encoder_mean(const uint8_t *boards, const float *embed_table, c
                               const void *weights_bf16, const float *params_f32, int n_layers, float *features,
                               int64_t B, void *stream);
 
+/* ---- policy network (inference, fp32 rollout): split-fp16 products on the matrix cores --------------------------------
+ * The reference rolls out in fp32 (src/ppo/torch_action_wrapper.py:73-102).  These four entry points are that forward with every
+ * activation between kernels f32 and every Linear of the encoder a two-way fp16 split product: v = (hi + lo) / s with
+ * hi = f16(s v), lo = f16(s v - hi), three f16 MFMAs per fragment pair (lo_w hi_x, hi_w lo_x, hi_w hi_x) into one f32
+ * accumulator, the result multiplied by 1 / (sx sw) in f32.  Scales are powers of two chosen by the caller with |s v| <= 2^15
+ * for every element (an element beyond fp16's range gives inf / NaN outputs, not a quietly wrong number); elements with
+ * |s v| >= 2^-3 keep 22 significand bits, smaller ones an absolute error of at most 2^-14 / s. */
+#define G2048_F32SPLIT_BIAS 0      /* y = x W^T + b */
+#define G2048_F32SPLIT_BIAS_RELU 1 /* y = relu(x W^T + b) */
+#define G2048_F32SPLIT_ADD_LN 2    /* y = resid + x W^T + b;  h = LayerNorm(y) * gamma + beta   (N = 256) */
+#define G2048_F32SPLIT_ADD 3       /* y = resid + x W^T + b                                     (N = 256) */
+
+/* Weight planes of one Linear (reference: the nn.Linear / in_proj weights read by torch_action_wrapper.py:73-102 through the agent).
+ * w f32 [N][K] row-major -> packed, 4 N K bytes of fp16: unit (((c K/16 + ks) 8 + nt) 2 + p) 64 + l (16 bytes each) holds plane p
+ * (0 hi, 1 lo) of w[256 c + 32 nt + (l & 31)][16 ks + 8 (l >> 5) + 0..7] * scale: the matrix-core A fragment of lane l.
+ * G2048_EINVAL: a null or misaligned (16 bytes) pointer, K not in {256, 1024}, N not in {256, 768, 1024}, scale not a power of two. */
+int g2048_f32split_pack(const float *w, int N, int K, float scale, void *packed, void *stream);
+
+/* One Linear of the fp32 rollout forward (torch_action_wrapper.py:73-102: in_proj, out_proj, linear1, linear2 of every encoder layer).
+ * x f32 [T][K] with row stride ldx; w_packed from g2048_f32split_pack with scale sw; bias f32 [N]; y f32 [T][N] with row stride ldy;
+ * epilogue one of G2048_F32SPLIT_*.  For ADD_LN / ADD: resid f32 [T][256] contiguous (y may be resid itself), and for ADD_LN gamma,
+ * beta f32 [256], h f32 [T][256] contiguous, eps > 0.  sx: the power of two x is multiplied by before it is split.  Rows past T and
+ * bytes outside the outputs are not written.
+ * G2048_EINVAL: a null or misaligned required pointer, T < 1, unsupported K / N (as above; N = 256 for ADD_LN / ADD), ldx < K,
+ * ldy < N, strides not multiples of 4, an unknown epilogue, sx or sw not a power of two. */
+int g2048_f32split_gemm(const float *x, int64_t ldx, const void *w_packed, const float *bias, float *y, int64_t ldy,
+                        const float *resid, const float *gamma, const float *beta, float *h, int64_t T, int K, int N,
+                        int epilogue, float sx, float sw, float eps, void *stream);
+
+/* Self-attention of the fp32 rollout forward (torch_action_wrapper.py:73-102 -> nn.TransformerEncoderLayer, eval mode: no dropout):
+ * 17 tokens, H heads of 32, qkv f32 [B][17][3 * 32 H] (the packed in_proj output, read in place), o f32 [B][17][32 H];
+ * softmax(scale q k^T) v in f32 FMAs.  G2048_EINVAL: a null or misaligned pointer, B < 1, H outside 1 .. 64. */
+int g2048_attn_fwd_f32(const float *qkv, float *o, int64_t B, int H, float scale, void *stream);
+
+/* Token embedding of the fp32 rollout forward (torch_action_wrapper.py:73-102 -> ppo_agent.py:59-66, transformer_encoder.py:150-190):
+ * x0[b][0] = cls, x0[b][1 + c] = table[c][boards[b][c]] (table f32 [16][31][256] = positional code + embedding row), and
+ * h = LayerNorm(x0) * gamma + beta (layers[0].norm1), both f32 [B][17][256].  G2048_EINVAL: a null or misaligned pointer, B < 1. */
+int g2048_embed_ln_f32(const uint8_t *boards, const float *table, const float *cls, const float *gamma, const float *beta, float eps,
+                       float *x0, float *h, int64_t B, void *stream);
+
 /* ---- one-ply expectimax over the critic (no reference counterpart: the reference only ever asks the actor) -----------
  * Q(s, a) = r(s, a) + gamma * E_{s' ~ spawn(after(s, a))} V(s'), V(terminal s') = 0, with the spawn law of the env (uniform
  * over the empty cells of the afterstate, tile 2 with p = 0.9, tile 4 with p = 0.1).  Three kernels around the caller's

@@ -1,6 +1,7 @@
 """Kernel breakdown of the collect phase (policy-in-the-loop rollout of 65536 boards with the bf16 Transformer).
-usage: python tools/probe_collect.py [boards] [--fp32] [--reduction {cls,mean}] [--unfused] [--no-profile]
+usage: python tools/probe_collect.py [boards] [--fp32] [--fp32-native] [--reduction {cls,mean}] [--unfused] [--no-profile]
   --fp32: the reference's rollout precision, the PyTorch fp32 module forward
+  --fp32-native: fp32 rollout through the split-fp16 kernels (FusedPolicyF32); implies --fp32
   --reduction: the agent's reduction (default cls, bench.py's model); "mean" is the reference PPOAgent's default
   --unfused: bf16 rollout without the fused encoder kernels (the layer kernels forward-only + library-GEMM heads)
   --no-profile: the collect wall time only"""
@@ -18,7 +19,8 @@ from src.ppo import PPOAgent, PPOTrainer, RolloutBuffer
 from src.runs import BatchRunner
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 65536
-FP32 = "--fp32" in sys.argv
+NATIVE = "--fp32-native" in sys.argv
+FP32 = "--fp32" in sys.argv or NATIVE
 RED = sys.argv[sys.argv.index("--reduction") + 1] if "--reduction" in sys.argv else "cls"
 assert RED in ("cls", "mean"), RED
 if "--unfused" in sys.argv:
@@ -29,7 +31,7 @@ dev = torch.device("cuda:0")
 torch.manual_seed(0)
 agent = PPOAgent(**dict(bench.MODEL_CFG, reduction=RED))
 tr = PPOTrainer(agent, BatchRunner(0, device=dev), RolloutBuffer(31, 16, 4), bench.OPTIM_CFG, max_steps=500000, device=dev,
-                rollout_amp=not FP32, log_dir="/tmp/lg", **bench.TRAINER_CFG)
+                rollout_amp=not FP32, log_dir="/tmp/lg", **bench.TRAINER_CFG, **(dict(fp32_native=True) if NATIVE else {}))
 tr.collect_rollouts(B, 1)
 tr.rollout_buffer.reset()
 torch.cuda.synchronize()
