@@ -715,58 +715,85 @@ def linear_ok(x2: torch.Tensor, weight: torch.Tensor) -> bool:
             and x2.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0 and x2.shape[0] > 0)
 
 
+def _out_rows(out: torch.Tensor, T: int, N: int, name: str) -> int:
+    """The leading dimension of a caller's bf16 [T, N] output: contiguous, or a row view (unit inner stride) of a wider buffer."""
+    if not out.is_cuda or out.dtype != torch.bfloat16 or out.dim() != 2 or tuple(out.shape) != (T, N) or out.stride(1) != 1:
+        raise NativeError(f"{name}: out must be a bf16 [{T}, {N}] device tensor with contiguous rows")
+    return N if out.is_contiguous() else out.stride(0)
+
+
 def linear_bf16(x2: torch.Tensor, weight: torch.Tensor, bias_f32=None, out=None) -> torch.Tensor:
-    """out[T, N] (bf16) = x2[T, K] @ weight[N, K]^T (+ bias f32 [N])."""
+    """out[T, N] (bf16) = x2[T, K] @ weight[N, K]^T (+ bias f32 [N]).  ``out``: contiguous with at least T * N elements, or a [T, N] row
+    view of a wider buffer (its row stride becomes ldy)."""
     if not linear_ok(x2, weight):
         raise NativeError(f"linear_bf16: unsupported operands {tuple(x2.shape)} {x2.dtype} x {tuple(weight.shape)} {weight.dtype}")
     T, K = x2.shape
     N = weight.shape[0]
     if out is None:
         out = torch.empty((T, N), dtype=torch.bfloat16, device=x2.device)
+    if out.is_contiguous():
+        out_ptr, ldy = _dev(out, torch.bfloat16, T * N, "out"), N
+    else:
+        out_ptr, ldy = out.data_ptr(), _out_rows(out, T, N, "linear_bf16")
     _check(load().g2048_linear_bf16(x2.data_ptr(), x2.stride(0), weight.data_ptr(), weight.stride(0),
-                                    _dev(bias_f32, f32, N, "bias", optional=True), _dev(out, torch.bfloat16, T * N, "out"), N, T,
-                                    K, N, _stream()), "g2048_linear_bf16")
+                                    _dev(bias_f32, f32, N, "bias", optional=True), out_ptr, ldy, T, K, N, _stream()), "g2048_linear_bf16")
     return out
 
 
 def linear_relu_dropout(x2: torch.Tensor, weight: torch.Tensor, bias_f32: torch.Tensor, p_drop: float, seed: int = 0,
-                        seed_state: int = 0, want_mask: bool = False):
+                        seed_state: int = 0, want_mask: bool = False, out=None, mask=None):
     """dropout(relu(x2 @ weight^T + bias)) -> bf16 [T, N] in one launch (K <= 256); see g2048_linear_relu_dropout_bf16.
-    ``want_mask``: -> (y, mask) with the opaque bit mask ``linear_mask_bwd`` reads."""
+    ``want_mask``: -> (y, mask) with the opaque bit mask ``linear_mask_bwd`` reads.  ``out`` (bf16 [T, N], contiguous or a row view of a
+    wider buffer) and ``mask`` (uint8, ``g2048_ffn_mask_bytes`` elements, 8-byte aligned; implies ``want_mask``) are written in place of
+    fresh allocations."""
     if not linear_ok(x2, weight) or x2.shape[1] > 256:
         raise NativeError(f"linear_relu_dropout: unsupported operands {tuple(x2.shape)} {x2.dtype} x {tuple(weight.shape)}")
     T, K = x2.shape
     N = weight.shape[0]
-    out = torch.empty((T, N), dtype=torch.bfloat16, device=x2.device)
-    mask = torch.empty(load().g2048_ffn_mask_bytes(T, N), dtype=u8, device=x2.device) if want_mask else None
+    if out is None:
+        out = torch.empty((T, N), dtype=torch.bfloat16, device=x2.device)
+    ldy = _out_rows(out, T, N, "linear_relu_dropout")
+    want_mask = want_mask or mask is not None
+    if mask is None:
+        mask = torch.empty(load().g2048_ffn_mask_bytes(T, N), dtype=u8, device=x2.device) if want_mask else None
+    elif (mask.dtype != u8 or not mask.is_cuda or not mask.is_contiguous() or mask.numel() != load().g2048_ffn_mask_bytes(T, N)
+          or mask.data_ptr() % 8):
+        raise NativeError(f"linear_relu_dropout: the mask buffer does not fit a [{T}, {N}] call")
     _check(load().g2048_linear_relu_dropout_bf16(x2.data_ptr(), x2.stride(0), weight.data_ptr(), weight.stride(0),
-                                                 _dev(bias_f32, f32, N, "bias"), out.data_ptr(), N, T, K, N, float(p_drop),
+                                                 _dev(bias_f32, f32, N, "bias"), out.data_ptr(), ldy, T, K, N, float(p_drop),
                                                  int(seed) & (2 ** 64 - 1), seed_state or None,
                                                  mask.data_ptr() if want_mask else None, _stream()),
            "g2048_linear_relu_dropout_bf16")
     return (out, mask) if want_mask else out
 
 
-def linear_mask_bwd(dy2: torch.Tensor, weight_t: torch.Tensor, mask: torch.Tensor, p_drop: float, final: bool = True):
+def linear_mask_bwd(dy2: torch.Tensor, weight_t: torch.Tensor, mask: torch.Tensor, p_drop: float, final: bool = True, out=None, db=None,
+                    workspace=None):
     """-> (dz bf16 [T, N], dbias f32 [N]): dz = (dy2 @ weight_t^T) / (1 - p) where the forward's output was non-zero
     (``mask`` from ``linear_relu_dropout(..., want_mask=True)`` with the same T and N); see g2048_linear_mask_bwd_bf16.
-    ``final`` False: (dz, partial sums f32 [rows, N]) for ``reduce_jobs``."""
+    ``final`` False: (dz, partial sums f32 [rows, N]) for ``reduce_jobs``.  ``out`` (bf16 [T, N], contiguous or a row view of a wider
+    buffer), ``db`` (f32 [N]) and ``workspace`` (f32, ``g2048_linear_mask_bwd_workspace_floats`` elements) are written in place of fresh
+    allocations."""
     if not linear_ok(dy2, weight_t) or dy2.shape[1] > 256:
         raise NativeError(f"linear_mask_bwd: unsupported operands {tuple(dy2.shape)} {dy2.dtype} x {tuple(weight_t.shape)}")
     T, K = dy2.shape
     N = weight_t.shape[0]
     if mask.dtype != u8 or not mask.is_cuda or mask.numel() != load().g2048_ffn_mask_bytes(T, N) or mask.data_ptr() % 8:
         raise NativeError(f"linear_mask_bwd: the mask does not belong to a [{T}, {N}] forward call")
-    dz = torch.empty((T, N), dtype=torch.bfloat16, device=dy2.device)
-    db = torch.empty(N, dtype=f32, device=dy2.device) if final else None
-    ws = torch.empty(load().g2048_linear_mask_bwd_workspace_floats(T, N), dtype=f32, device=dy2.device)
+    dz = torch.empty((T, N), dtype=torch.bfloat16, device=dy2.device) if out is None else out
+    lddz = _out_rows(dz, T, N, "linear_mask_bwd")
+    if final and db is None:
+        db = torch.empty(N, dtype=f32, device=dy2.device)
+    ws_floats = load().g2048_linear_mask_bwd_workspace_floats(T, N)
+    ws = torch.empty(ws_floats, dtype=f32, device=dy2.device) if workspace is None else workspace
     _check(load().g2048_linear_mask_bwd_bf16(dy2.data_ptr(), dy2.stride(0), weight_t.data_ptr(), weight_t.stride(0),
-                                             mask.data_ptr(), dz.data_ptr(), N, db.data_ptr() if final else None, ws.data_ptr(),
-                                             T, K, N, float(p_drop), _stream()), "g2048_linear_mask_bwd_bf16")
+                                             mask.data_ptr(), dz.data_ptr(), lddz, _dev(db, f32, N, "db") if final else None,
+                                             _dev(ws, f32, ws_floats, "workspace"), T, K, N, float(p_drop), _stream()),
+           "g2048_linear_mask_bwd_bf16")
     if final:
         return dz, db
     rows = load().g2048_linear_mask_bwd_partial_rows(T, N)
-    return dz, ws[:rows * N].view(rows, N)
+    return dz, ws.view(-1)[:rows * N].view(rows, N)
 
 
 def embed_fwd(boards, wt, pe, cls, x0, p_drop: float = 0.0, seed: int = 0, seed_state: int = 0, ln=None):
@@ -1051,17 +1078,22 @@ def dweight_ok(dy2: torch.Tensor, x2: torch.Tensor, slices: int) -> bool:
     return N % 128 == 0 and K % 128 == 0 and T > 0 and T % (64 * slices) == 0 and (slices < 8 or slices % 8 == 0)
 
 
-def dweight_parts(dy2: torch.Tensor, x2: torch.Tensor, slices: int, out: torch.Tensor = None, block_rows: int = 0, colsum: bool = False):
+def dweight_parts(dy2: torch.Tensor, x2: torch.Tensor, slices: int, out: torch.Tensor = None, block_rows: int = 0, colsum: bool = False,
+                  colsum_out: torch.Tensor = None):
     """bf16 [slices, N, K] whose sum over the first axis is dY^T X (``g2048_dweight_bf16``); with ``colsum`` also f32 [slices, N] whose
-    sum over the first axis is ``dy2.sum(0)``: -> (parts, column sums)."""
+    sum over the first axis is ``dy2.sum(0)``: -> (parts, column sums).  ``colsum_out`` (f32, slices * N elements; implies ``colsum``) is
+    written in place of a fresh allocation."""
     if not dweight_ok(dy2, x2, slices):
         raise NativeError(f"dweight_parts: operands {tuple(dy2.shape)} x {tuple(x2.shape)} with {slices} slices are not supported")
     T, N, K = dy2.shape[0], dy2.shape[1], x2.shape[1]
     if out is None:
         out = torch.empty((slices, N, K), dtype=torch.bfloat16, device=dy2.device)
-    cs = torch.empty((slices, N), dtype=f32, device=dy2.device) if colsum else None
+    colsum = colsum or colsum_out is not None
+    cs = None
+    if colsum:
+        cs = torch.empty((slices, N), dtype=f32, device=dy2.device) if colsum_out is None else colsum_out
     _check(load().g2048_dweight_bf16(dy2.data_ptr(), dy2.stride(0), x2.data_ptr(), x2.stride(0), _dev(out, torch.bfloat16, slices * N * K, "parts"),
-                                     None if cs is None else cs.data_ptr(), T, N, K, int(slices), int(block_rows), _stream()),
+                                     None if cs is None else _dev(cs, f32, slices * N, "colsum"), T, N, K, int(slices), int(block_rows), _stream()),
            "g2048_dweight_bf16")
     return (out, cs) if colsum else out
 
