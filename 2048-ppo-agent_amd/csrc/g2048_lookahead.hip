@@ -8,6 +8,14 @@
 // movers: per board expand reads 16 B and writes 96 B, children writes 17 B per child (at most 120 children per board,
 // a few dozen in play), reduce reads 5 B per child.  No LDS, no atomics; the children are written with vector stores,
 // one 16-byte store per lane, consecutive lanes to consecutive rows (1 KiB per wave-instruction).
+//
+// Two plies (include/g2048.h, "two-ply") run the same three kernels on both levels and add two between them:
+//
+//   dedup     the afterstates of one root's (child, action) pairs -> the first pair with the same 16 bytes, per root
+//   backup    level-2 expectations -> V1 of every level-1 child, the max over its legal actions
+//
+// dedup is the only kernel here with LDS: one workgroup per root stages the root's keys (at most 480 x 16 B) and every lane
+// scans the keys before its own pair.  backup is a byte mover like the others (48 B read, 4 gathers, 4 B written per child).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -121,6 +129,85 @@ __global__ void __launch_bounds__(kBlock) k_lookahead_reduce(const float *reward
     q[p] = add_rn(reward[p], mul_rn(gamma, acc / (float)ne));
 }
 
+// One workgroup per root.  The keys are staged linearly, 16 B per pair: in the scan every lane of a wave reads the SAME key q
+// (one ds_read_b128 whose 64 addresses are identical broadcasts, so no layout can conflict), compares it with its own key in
+// registers and stops at its first match; a wave runs to the longest scan among its lanes.  A pair without children is staged
+// as a key no board has (0xFF in every cell), so it matches nothing and nothing matches it.  Each pair is written by exactly one
+// lane and read-only state decides what it writes: no atomics, no dependence on scheduling.  A group whose bounds disagree
+// (negative, past P, more than kMaxGroup pairs) gets rep = p, nuniq = 0 on the part of its range inside [0, P): no child of it
+// is valued, its actions back up 0; a decreasing pair of bounds writes nothing.
+constexpr int kDedupBlock = 128;
+constexpr int kMaxGroup = 480;  // 120 level-1 children x 4 actions
+
+__global__ void __launch_bounds__(kDedupBlock) k_lookahead_dedup(const uint8_t *after, const int32_t *nchild, const int32_t *group_start,
+                                                                 int64_t P, int32_t *rep, int32_t *nuniq) {
+    __shared__ uint4 keys[kMaxGroup];
+    const int64_t s = group_start[blockIdx.x], e = group_start[blockIdx.x + 1];
+    if (s < 0 || e < s || e > P || e - s > kMaxGroup) {  // uniform over the block: nobody waits at the barrier below
+        // benign on inconsistent bounds: what of the range lies inside [0, P) is left without duplicates and without children
+        const int64_t lo = s < 0 ? 0 : s, hi = e > P ? P : e;
+        for (int64_t i = lo + threadIdx.x; i < hi; i += kDedupBlock) {
+            rep[i] = (int32_t)i;
+            nuniq[i] = 0;
+        }
+        return;
+    }
+    const int n = (int)(e - s);
+    uint4 mine[(kMaxGroup + kDedupBlock - 1) / kDedupBlock];
+    int32_t cnt[(kMaxGroup + kDedupBlock - 1) / kDedupBlock];
+#pragma unroll
+    for (int k = 0; k < (kMaxGroup + kDedupBlock - 1) / kDedupBlock; ++k) {
+        const int i = k * kDedupBlock + (int)threadIdx.x;
+        if (i < n) {
+            cnt[k] = nchild[s + i];
+            mine[k] = cnt[k] > 0 ? reinterpret_cast<const uint4 *>(after)[s + i] : make_uint4(~0u, ~0u, ~0u, ~0u);
+            keys[i] = mine[k];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < (kMaxGroup + kDedupBlock - 1) / kDedupBlock; ++k) {
+        const int i = k * kDedupBlock + (int)threadIdx.x;
+        if (i >= n) continue;
+        int first = i;
+        if (cnt[k] > 0) {
+            for (int q = 0; q < i; ++q) {
+                const uint4 o = keys[q];
+                // one 128-bit read and a branch-free compare (&& would fetch the key a dword at a time)
+                if (((o.x ^ mine[k].x) | (o.y ^ mine[k].y) | (o.z ^ mine[k].z) | (o.w ^ mine[k].w)) == 0u) {
+                    first = q;
+                    break;
+                }
+            }
+        }
+        rep[s + i] = (int32_t)(s + first);
+        nuniq[s + i] = first == i ? cnt[k] : 0;
+    }
+}
+
+// One lane per level-1 child: its four rewards, counts and representatives are one 16-byte load each, the expectations four
+// gathers.  A representative outside [0, P) (inconsistent inputs) removes the action like a count of 0 does.
+__global__ void __launch_bounds__(kBlock) k_lookahead_backup(const float *reward, const int32_t *nchild, const int32_t *rep,
+                                                             const float *e, int64_t N1, float *v1) {
+    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= N1) return;
+    const float4 r4 = reinterpret_cast<const float4 *>(reward)[c];
+    const int4 n4 = reinterpret_cast<const int4 *>(nchild)[c];
+    const int4 p4 = reinterpret_cast<const int4 *>(rep)[c];
+    const float r[4] = {r4.x, r4.y, r4.z, r4.w};
+    const int32_t n[4] = {n4.x, n4.y, n4.z, n4.w}, p[4] = {p4.x, p4.y, p4.z, p4.w};
+    bool any = false;
+    float best = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        if (n[a] <= 0 || p[a] < 0 || (int64_t)p[a] >= 4 * N1) continue;
+        const float x = add_rn(r[a], e[p[a]]);
+        best = (!any || x > best) ? x : best;
+        any = true;
+    }
+    v1[c] = best;
+}
+
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 }  // namespace
@@ -153,6 +240,27 @@ int g2048_lookahead_reduce(const float *reward, const int32_t *nchild, const int
         return G2048_EINVAL;
     hipLaunchKernelGGL(k_lookahead_reduce, dim3(blocks_for(4 * B)), dim3(kBlock), 0, (hipStream_t)stream, reward, nchild, offset, values,
                        terminal, (float)gamma, 4 * B, N, q);
+    return launch_status();
+}
+
+int g2048_lookahead_dedup(const uint8_t *after, const int32_t *nchild, const int32_t *group_start, int64_t G, int64_t P, int32_t *rep,
+                          int32_t *nuniq, void *stream) {
+    if (!after || !nchild || !group_start || !rep || !nuniq || G <= 0 || G > kMaxBoards || P < 0 || P > 4 * kMaxBoards ||
+        P > kMaxGroup * G || (P & 3))
+        return G2048_EINVAL;
+    if (!aligned16(after) || ((uintptr_t)nchild & 3) || ((uintptr_t)group_start & 3) || ((uintptr_t)rep & 3) || ((uintptr_t)nuniq & 3))
+        return G2048_EINVAL;
+    if (P == 0) return 0;
+    hipLaunchKernelGGL(k_lookahead_dedup, dim3((unsigned)G), dim3(kDedupBlock), 0, (hipStream_t)stream, after, nchild, group_start, P, rep,
+                       nuniq);
+    return launch_status();
+}
+
+int g2048_lookahead_backup(const float *reward, const int32_t *nchild, const int32_t *rep, const float *e, int64_t N1, float *v1,
+                           void *stream) {
+    if (!reward || !nchild || !rep || !e || !v1 || N1 <= 0 || N1 > kMaxBoards) return G2048_EINVAL;
+    if (!aligned16(reward, nchild, rep) || ((uintptr_t)e & 3) || ((uintptr_t)v1 & 3)) return G2048_EINVAL;
+    hipLaunchKernelGGL(k_lookahead_backup, dim3(blocks_for(N1)), dim3(kBlock), 0, (hipStream_t)stream, reward, nchild, rep, e, N1, v1);
     return launch_status();
 }
 

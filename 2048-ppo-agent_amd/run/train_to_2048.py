@@ -48,7 +48,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--seed", type=int, default=0, help="seed of the weights, the environments and the minibatch order")
     ap.add_argument("--eval-lookahead", type=int, default=0,
-                    help="1: every evaluation point also plays one-ply expectimax over the critic on the same seeds (key 'lookahead')")
+                    help="1 / 2: every evaluation point also plays one- / two-ply expectimax over the critic on the same seeds (key 'lookahead')")
+    ap.add_argument("--eval-episodes", type=int, default=1000, help="episodes per evaluation (a two-ply evaluation can be sized)")
     ap.add_argument("--save-agent", default=None, help="write the final agent's state_dict here (tools/probe_lookahead.py reads it)")
     a = ap.parse_args()
 
@@ -66,12 +67,14 @@ def main():
                     **TRAINER)
 
     def evaluate(minutes):
-        ev = evaluate_agent(agent, dev, 1000) if rank == 0 else None
+        ev = evaluate_agent(agent, dev, a.eval_episodes) if rank == 0 else None
         if ev is not None and a.eval_lookahead:
-            # the same 1000 episodes' seeds, the same weights; the greedy figures keep their keys (earlier result files stay comparable)
+            # the same episodes' seeds, the same weights; the greedy figures keep their keys (earlier result files stay comparable)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            la = evaluate_agent(agent, dev, 1000, lookahead=a.eval_lookahead, gamma=TRAINER["gamma"])
+            # depth 2 is ExpectimaxActionFunction (the one-ply class keeps depth=1 only); any other depth raises as before
+            search = dict(expectimax=2) if a.eval_lookahead == 2 else dict(lookahead=a.eval_lookahead)
+            la = evaluate_agent(agent, dev, a.eval_episodes, gamma=TRAINER["gamma"], **search)
             torch.cuda.synchronize()
             la.update(depth=a.eval_lookahead, gamma=TRAINER["gamma"], eval_seconds=round(time.perf_counter() - t0, 1))
             ev["lookahead"] = la

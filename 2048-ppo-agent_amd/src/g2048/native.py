@@ -55,6 +55,8 @@ SIGNATURES = {
     "g2048_lookahead_expand": [_vp, _i64, _vp, _vp, _vp, _vp],
     "g2048_lookahead_children": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
     "g2048_lookahead_reduce": [_vp, _vp, _vp, _vp, _vp, _dbl, _i64, _i64, _vp, _vp],
+    "g2048_lookahead_dedup": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "g2048_lookahead_backup": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "g2048_attn_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, C.c_float,
                        C.c_float, C.c_uint64, _vp, _vp],
     "g2048_attn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -434,6 +436,28 @@ def lookahead_reduce(reward, nchild, offset, values, terminal, gamma: float, N: 
                                          _dev(offset, i32, 4 * B, "offset"), _dev(values, f32, N, "values"),
                                          _dev(terminal, u8, N, "terminal"), float(gamma), B, N, _dev(q, f32, 4 * B, "q"), _stream()),
            "g2048_lookahead_reduce")
+
+
+def lookahead_dedup(after, nchild, group_start, rep, nuniq):
+    """Per root (pairs group_start[g] .. group_start[g + 1], at most 480): rep i32 [P] = the first pair of the group with children
+    and the same afterstate bytes (itself where nchild == 0), nuniq i32 [P] = nchild at representatives, 0 elsewhere."""
+    P = nchild.numel()
+    G = group_start.numel() - 1
+    if G < 1:
+        raise NativeError("lookahead_dedup: group_start needs at least two entries")
+    _check(load().g2048_lookahead_dedup(_dev(after, u8, 16 * P, "after"), _dev(nchild, i32, P, "nchild"),
+                                        _dev(group_start, i32, G + 1, "group_start"), G, P, _dev(rep, i32, P, "rep"),
+                                        _dev(nuniq, i32, P, "nuniq"), _stream()),
+           "g2048_lookahead_dedup")
+
+
+def lookahead_backup(reward, nchild, rep, e, v1):
+    """v1 f32 [N1] = max over the actions with nchild > 0 of reward + e[rep] (0 where there is none); the others are [N1,4]."""
+    N1 = nchild.numel() // 4
+    _check(load().g2048_lookahead_backup(_dev(reward, f32, 4 * N1, "reward"), _dev(nchild, i32, 4 * N1, "nchild"),
+                                         _dev(rep, i32, 4 * N1, "rep"), _dev(e, f32, 4 * N1, "e"), N1,
+                                         _dev(v1, f32, N1, "v1"), _stream()),
+           "g2048_lookahead_backup")
 
 
 def attn_fwd(q_ptr: int, k_ptr: int, v_ptr: int, o, lse, B: int, H: int, Sq: int, strides, scale: float, p_drop: float,

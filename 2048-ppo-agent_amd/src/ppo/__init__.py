@@ -1,4 +1,5 @@
 from .data_loader import create_ppo_dataloader
+from .expectimax import ExpectimaxActionFunction
 from .lookahead import LookaheadActionFunction
 from .ppo_agent import MLPAgent, PPOAgent
 from .ppo_trainer import PPOTrainer

@@ -43,14 +43,24 @@ def evaluate_max_tile(act_fn: Callable, num_episodes: int = 1000, seed: int = 42
 
 
 def evaluate_agent(agent, device, num_episodes: int = 1000, seed: int = 42, rng_mode=None, lookahead: int = 0,
-                   gamma: float = 0.99) -> Dict:
+                   gamma: float = 0.99, expectimax: int = 0) -> Dict:
     """Greedy, masked evaluation of a PPO agent (run/viz_ppo_agent.py:267-300).  ``lookahead=1``: the same protocol (same
     seeds, same env and key stream) played by one-ply expectimax over the agent's critic with discount ``gamma``
-    (``LookaheadActionFunction``) instead of the actor's argmax; ``lookahead=0`` is the reference's evaluation."""
+    (``LookaheadActionFunction``) instead of the actor's argmax; ``lookahead=0`` is the reference's evaluation.  ``expectimax=2``: the same
+    protocol played by two-ply expectimax (``ExpectimaxActionFunction``); it excludes ``lookahead``, whose only depth stays 1, and takes
+    no other value than 0 and 2 (one ply is spelled ``lookahead=1``)."""
     from ..ppo.torch_action_wrapper import TorchActionFunction
 
+    if lookahead and expectimax:
+        raise ValueError("evaluate_agent: lookahead and expectimax are mutually exclusive")
+    if expectimax not in (0, 2):
+        raise ValueError(f"evaluate_agent: expectimax is 0 (off) or 2 plies, got {expectimax!r}; one ply is lookahead=1")
     was_training = agent.training
-    if lookahead:
+    if expectimax:
+        from ..ppo.expectimax import ExpectimaxActionFunction
+
+        fn = ExpectimaxActionFunction(agent, plies=expectimax, gamma=gamma, device=device)
+    elif lookahead:
         from ..ppo.lookahead import LookaheadActionFunction
 
         fn = LookaheadActionFunction(agent, gamma=gamma, depth=lookahead, device=device)

@@ -264,6 +264,36 @@ int g2048_lookahead_children(const uint8_t *after, const int32_t *nchild, const 
 int g2048_lookahead_reduce(const float *reward, const int32_t *nchild, const int32_t *offset, const float *values,
                            const uint8_t *terminal, double gamma, int64_t B, int64_t N, float *q, void *stream);
 
+/* ---- two-ply expectimax over the critic --------------------------------------------------------------------------------
+ * V1(s') = 0 if s' is terminal, else max over the legal a' of [ r(s', a') + gamma * E_spawn V(s'') ], V(terminal s'') = 0;
+ * Q2(s, a) = r(s, a) + gamma * E_spawn V1(s').  The three kernels above run on both levels (a level-1 child is a board):
+ * expand(boards) -> children -> expand(children1) -> dedup -> children(after2, nuniq) -> V(children2) ->
+ * reduce(reward = 0, nuniq) = e -> backup = V1 -> reduce(reward1, nchild1, values = V1) = Q2.  The level-2 pairs are indexed
+ * p = 4 * c + a' over the N1 level-1 children c; the pairs of one root are contiguous (its children are). */
+
+/* Duplicate afterstates within each root.  group_start i32[G + 1] (device): root g owns the pairs group_start[g] ..
+ * group_start[g + 1], at most 480 (120 children x 4 actions), group_start[G] = P = 4 * N1.  For a pair p with nchild[p] > 0,
+ * rep[p] = the smallest p' of the same group with nchild[p'] > 0 and the same 16 bytes after[p']; for nchild[p] = 0, rep[p] = p.
+ * nuniq[p] = nchild[p] if rep[p] = p, else 0: the counts of the children that still need a value.  Two pairs with one
+ * afterstate have the same spawn children, hence the same expectation.  One workgroup per root, the root's keys staged in LDS
+ * (at most 7680 B), every lane scans the keys before its own pair; no atomics, the output does not depend on scheduling.
+ * rep / nuniq i32[P]; entries at or past P are not touched.  group_start lives on the device, so a group whose bounds disagree
+ * (negative, past P, more than 480 pairs) cannot be refused by the host: the kernel gives the part of its range inside 0 .. P
+ * rep = p, nuniq = 0 (no child of it is valued), and a decreasing pair of bounds writes nothing.  P = 0 launches nothing.
+ * G2048_EINVAL: a null pointer, G outside 1 .. 2^24, P < 0, P not a multiple of 4, P > 2^26, P > 480 * G (some group would
+ * be larger than 480 pairs), after not 16-byte aligned, the others not 4-byte aligned. */
+int g2048_lookahead_dedup(const uint8_t *after, const int32_t *nchild, const int32_t *group_start, int64_t G, int64_t P, int32_t *rep,
+                          int32_t *nuniq, void *stream);
+
+/* v1 f32[N1]: v1[c] = max over the a' with nchild[c][a'] > 0 of reward[c][a'] + e[rep[c][a']] (each sum rounded to f32, the
+ * max exact), 0 if there is none.  e f32[4 * N1] is g2048_lookahead_reduce's output with an all-zero reward on the nuniq
+ * counts: gamma * mean at representatives (0 + x is exact, so reward + e[rep] rounds as reward + gamma * mean does without
+ * dedup).  One lane per level-1 child, one 16-byte load each of its rewards, counts and reps; a rep outside 0 .. 4 * N1
+ * removes the action.  G2048_EINVAL: a null pointer, N1 outside 1 .. 2^24, reward / nchild / rep not 16-byte aligned, e / v1
+ * not 4-byte aligned. */
+int g2048_lookahead_backup(const float *reward, const int32_t *nchild, const int32_t *rep, const float *e, int64_t N1, float *v1,
+                           void *stream);
+
 /* ---- policy network (update): attention for 17-token sequences ------------------------------------- */
 
 /* softmax(q k^T * scale) v with attention dropout, head_dim 32, Sk = 17 keys, Sq = 17 queries (or 1: the CLS row

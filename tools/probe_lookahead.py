@@ -2,12 +2,16 @@
 """Cost of one lock-step of one-ply expectimax play next to a greedy lock-step, on one GPU.
 
     python tools/probe_lookahead.py [--agent state_dict.pt] [--boards 100 65536] [--repeats 7] [--out result.json]
+    python tools/probe_lookahead.py --plies 2 [--no-dedup] [--boards 100 4096] ...
 
 For each batch size: boards that the agent's own greedy play visits (half an episode's worth of lock-steps into a rollout, so the
 fill of the boards is that of real play), then, with HIP events after a warm-up, the time of
   greedy     TorchActionFunction.policy_fn (bf16, the fused encoder for a default-shape agent)
   lookahead  LookaheadActionFunction.policy_fn on the same boards (same precision, same encoder on every child)
 and of the parts of the lookahead lock-step: the three new kernels, the prefix sum with its host read, the value forward.
+``--plies 2`` times the two-ply lock-step (ExpectimaxActionFunction, one slice of roots) and each of its parts instead: both
+expands, the dedup kernel, both prefix sums with their host reads, both children launches, the value forward, both reduces and
+the backup, with ``rows`` (value-forward rows) and ``rows_full`` (the rows without dedup); ``--no-dedup`` skips the dedup launch.
 Every figure is the median of ``--repeats`` timed repeats with the min and max next to it.  Prints one JSON line.
 """
 import argparse
@@ -22,7 +26,7 @@ sys.path.insert(0, os.path.join(HERE, "..", "2048-ppo-agent_amd"))
 import torch  # noqa: E402
 
 from src.g2048 import native as nv  # noqa: E402
-from src.ppo import LookaheadActionFunction, PPOAgent, TorchActionFunction  # noqa: E402
+from src.ppo import ExpectimaxActionFunction, LookaheadActionFunction, PPOAgent, TorchActionFunction  # noqa: E402
 from src.runs import BatchRunner  # noqa: E402
 
 MODEL = dict(observation_dim=31, action_dim=4, hidden_dim=512, d_model=256, nhead=8, num_layers=4, dim_feedforward=1024,
@@ -100,12 +104,89 @@ def probe(agent, B, dev, repeats):
     return res
 
 
+def probe2(agent, B, dev, repeats, dedup):
+    """The two-ply lock-step and its parts on the tensors of one expansion (a single slice of roots)."""
+    boards = mid_game_boards(agent, B, dev)
+    fn = ExpectimaxActionFunction(agent, plies=2, dedup=dedup, device=dev, amp_dtype=torch.bfloat16)
+    res = {"boards": B, "dedup": dedup, "fused_encoder": fn._fused is not None,
+           "lockstep": timed(lambda: fn.policy_fn(boards, None), repeats)}
+    res["rows"], res["rows_full"] = fn.last_children, fn.last_children_full
+    res["rows_over_rows_full"] = round(fn.last_children / max(fn.last_children_full, 1), 4)
+    i32, u8, f32 = torch.int32, torch.uint8, torch.float32
+    after1 = torch.empty((B, 4, 16), dtype=u8, device=dev)
+    reward1 = torch.empty((B, 4), dtype=f32, device=dev)
+    nchild1 = torch.empty((B, 4), dtype=i32, device=dev)
+    nv.lookahead_expand(boards, after1, reward1, nchild1)
+    incl1 = torch.cumsum(nchild1.view(-1), 0, dtype=i32)
+    offset1 = (incl1 - nchild1.view(-1)).view(B, 4)
+    N1 = int(incl1[-1].item())
+    if N1 > fn.max_children:
+        raise SystemExit(f"{B} boards have {N1} level-1 children: more than one slice of {fn.max_children}; probe a smaller batch")
+    res["level1_children"] = N1
+    children1 = torch.empty((N1, 16), dtype=u8, device=dev)
+    terminal1 = torch.empty(N1, dtype=u8, device=dev)
+    nv.lookahead_children(after1, nchild1, offset1, N1, children1, terminal1)
+    after2 = torch.empty((N1, 4, 16), dtype=u8, device=dev)
+    reward2 = torch.empty((N1, 4), dtype=f32, device=dev)
+    nchild2 = torch.empty((N1, 4), dtype=i32, device=dev)
+    nv.lookahead_expand(children1, after2, reward2, nchild2)
+    group_start = torch.cat([offset1[:, 0] * 4, torch.tensor([4 * N1], dtype=i32, device=dev)]).to(i32)
+    rep = torch.arange(4 * N1, dtype=i32, device=dev).view(N1, 4)
+    nuniq = nchild2.clone()
+    if dedup:
+        nv.lookahead_dedup(after2, nchild2, group_start, rep, nuniq)
+    incl2 = torch.cumsum(nuniq.view(-1), 0, dtype=i32)
+    offset2 = (incl2 - nuniq.view(-1)).view(N1, 4)
+    N2 = int(incl2[-1].item())
+    assert N2 == fn.last_children
+    children2 = torch.empty((N2, 16), dtype=u8, device=dev)
+    terminal2 = torch.empty(N2, dtype=u8, device=dev)
+    values = torch.empty(N2, dtype=f32, device=dev)
+    nv.lookahead_children(after2, nuniq, offset2, N2, children2, terminal2)
+    zero2 = torch.zeros_like(reward2)
+    e = torch.empty((N1, 4), dtype=f32, device=dev)
+    v1 = torch.empty(N1, dtype=f32, device=dev)
+    q2 = torch.empty((B, 4), dtype=f32, device=dev)
+
+    def scan1():
+        c = torch.cumsum(nchild1.view(-1), 0, dtype=i32)
+        (c - nchild1.view(-1)).view(B, 4)
+        return c[3::4].tolist()
+
+    def scan2():
+        c = torch.cumsum(nuniq.view(-1), 0, dtype=i32)
+        (c - nuniq.view(-1)).view(N1, 4)
+        return torch.stack((c[-1], nchild2.sum(dtype=i32))).tolist() if dedup else int(c[-1].item())
+
+    def forward():
+        for c0 in range(0, N2, fn.max_children):
+            values[c0:c0 + fn.max_children] = fn._values(children2[c0:c0 + fn.max_children])
+
+    parts = {"expand1": timed(lambda: nv.lookahead_expand(boards, after1, reward1, nchild1), repeats),
+             "scan1_and_host_read": timed(scan1, repeats),
+             "children1": timed(lambda: nv.lookahead_children(after1, nchild1, offset1, N1, children1, terminal1), repeats),
+             "expand2": timed(lambda: nv.lookahead_expand(children1, after2, reward2, nchild2), repeats)}
+    if dedup:
+        parts["dedup"] = timed(lambda: nv.lookahead_dedup(after2, nchild2, group_start, rep, nuniq), repeats)
+    parts.update({
+        "scan2_and_host_read": timed(scan2, repeats),
+        "children2": timed(lambda: nv.lookahead_children(after2, nuniq, offset2, N2, children2, terminal2), repeats),
+        "value_forward": timed(forward, repeats),
+        "reduce2": timed(lambda: nv.lookahead_reduce(zero2, nuniq, offset2, values, terminal2, fn.gamma, N2, e), repeats),
+        "backup": timed(lambda: nv.lookahead_backup(reward2, nchild2, rep, e, v1), repeats),
+        "reduce1": timed(lambda: nv.lookahead_reduce(reward1, nchild1, offset1, v1, terminal1, fn.gamma, N1, q2), repeats)})
+    res["parts"] = parts
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--agent", default=None, help="state_dict of a default-shape PPOAgent (run/train_to_2048.py --save-agent); default: fresh weights")
     ap.add_argument("--boards", type=int, nargs="+", default=[100, 65536])
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--plies", type=int, default=1, choices=[1, 2], help="2: the two-ply lock-step and its parts")
+    ap.add_argument("--no-dedup", action="store_true", help="with --plies 2: value every afterstate's children")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -119,7 +200,9 @@ def main():
     agent = agent.to(dev).eval()
     res = {"agent": os.path.basename(a.agent) if a.agent else "fresh weights", "precision": "bfloat16", "repeats": a.repeats,
            "timer": "HIP events around one policy_fn call, 3 warm-up calls, median [min, max]",
-           "runs": [probe(agent, B, dev, a.repeats) for B in a.boards]}
+           "plies": a.plies,
+           "runs": [probe(agent, B, dev, a.repeats) if a.plies == 1 else probe2(agent, B, dev, a.repeats, not a.no_dedup)
+                    for B in a.boards]}
     print(json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)) or ".", exist_ok=True)
