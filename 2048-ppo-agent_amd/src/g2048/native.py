@@ -100,6 +100,8 @@ SIGNATURES = {
     "g2048_dweight_t": [_vp, _i32, _i64, _i64, _i32, _vp],
     "g2048_dweight_bf16": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp],
     "g2048_dweight_jobs": [_vp, _i32, _vp],
+    "g2048_dweight_jobs_tiled": [_vp, _i32, _i32, _vp],
+    "g2048_dweight_jobs_plan": [_vp, _i32, _i32, _i32, _vp],
     "g2048_opt_workspace_floats": [_i32],
     "g2048_opt_step": [_vp, _i32, _vp, _vp, _vp, _vp, _i32, C.c_float, _vp, _i32, _vp, _vp, C.c_float, C.c_float, _i32, _vp, _vp, _vp],
     "g2048_lamb_workspace_floats": [_i32],
@@ -1130,9 +1132,20 @@ class DwgJob(C.Structure):
 DWG_MAX_JOBS = 16
 
 
-def dweight_jobs(jobs):
-    """Several ``dweight_parts`` products in one launch per ``DWG_MAX_JOBS`` (``g2048_dweight_jobs``).  jobs: (dy2, x2, parts bf16
-    (or f32: the job's ``parts_f32`` flag) [slices, N, K], colsum f32 [slices, N] or None); slices (= parts.shape[0]) a multiple of 8."""
+def dweight_jobs_plan(shapes, big_cells: int = -1, cus: int = 0):
+    """The block shapes ``g2048_dweight_jobs_tiled`` gives a launch of jobs of these (N, K, slices) on ``cus`` compute units: per job the
+    number of leading [256 x 256] cells computed as one block each (the rest: [128 x 128] blocks).  Host arithmetic only."""
+    recs = [DwgJob(None, None, None, None, 0, 0, 0, N, K, slices, 0) for N, K, slices in shapes]
+    arr, out = (DwgJob * len(recs))(*recs), (_i32 * len(recs))()
+    _check(load().g2048_dweight_jobs_plan(C.cast(arr, _vp), len(recs), int(big_cells), int(cus), C.cast(out, _vp)), "g2048_dweight_jobs_plan")
+    return list(out)
+
+
+def dweight_jobs(jobs, big_cells: int = -1):
+    """Several ``dweight_parts`` products in one launch per ``DWG_MAX_JOBS`` (``g2048_dweight_jobs_tiled``).  jobs: (dy2, x2, parts bf16
+    (or f32: the job's ``parts_f32`` flag) [slices, N, K], colsum f32 [slices, N] or None); slices (= parts.shape[0]) a multiple of 8.
+    ``big_cells``: how many [256 x 256] cells of each launch's jobs, in job order, are computed as one block (the rest as [128 x 128]
+    blocks; the partials are the same bits either way); -1: the entry point's choice for the device."""
     recs = []
     for dy2, x2, parts, cs in jobs:
         slices = parts.shape[0]
@@ -1147,7 +1160,7 @@ def dweight_jobs(jobs):
     for i in range(0, len(recs), DWG_MAX_JOBS):
         chunk = recs[i:i + DWG_MAX_JOBS]
         arr = (DwgJob * len(chunk))(*chunk)
-        _check(load().g2048_dweight_jobs(C.cast(arr, _vp), len(chunk), _stream()), "g2048_dweight_jobs")
+        _check(load().g2048_dweight_jobs_tiled(C.cast(arr, _vp), len(chunk), int(big_cells), _stream()), "g2048_dweight_jobs_tiled")
 
 
 def dweight_t(jobs, ld: int, m: int, slices: int):

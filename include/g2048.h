@@ -464,9 +464,16 @@ int g2048_dweight_bf16(const void *dy, int64_t lddy, const void *x, int64_t ldx,
                        int K, int slices, int block_rows, void *stream);
 
 /* The same for several Linears in ONE launch (the weight gradients of a whole backward pass, deferred to its end by the caller):
- * job j is g2048_dweight_bf16(dy, lddy, x, ldx, parts, colsum, T, N, K, slices, 128) with slices a multiple of 8.  jobs: host array,
- * read during the call.  parts_f32 != 0: the job's partials are stored as f32 [slices][N][K] instead of bf16 (twice the bytes into
- * g2048_reduce_jobs; the switch behind profiles/round4_dweight_slices_seeds.txt). */
+ * job j computes what g2048_dweight_bf16(dy, lddy, x, ldx, parts, colsum, T, N, K, slices, 128) does, bit for bit, with slices a multiple
+ * of 8.  jobs: host array, read during the call.  parts_f32 != 0: the job's partials are stored as f32 [slices][N][K] instead of bf16
+ * (twice the bytes into g2048_reduce_jobs; the switch behind profiles/round4_dweight_slices_seeds.txt).
+ * Block shapes: a job whose N and K are multiples of 256 is cut into [256 x 256] cells, row-major; its first n_big cells are one
+ * [256 x 256] block each (1.5 transposed LDS reads per MFMA instead of 3), every other cell four [128 x 128] blocks; all [256 x 256]
+ * blocks of the launch come first in the grid.  g2048_dweight_jobs_plan writes n_big[j] for a launch on `cus` compute units (host
+ * arithmetic only; the pointers of the jobs are not read): big_cells >= 0 deals that many cells to the jobs in order, big_cells < 0 is
+ * the launch's own choice - whole rounds of the chip in [256 x 256] blocks, the remainder in [128 x 128] blocks where that is at most
+ * two rounds of them.  g2048_dweight_jobs_tiled launches with that plan (big_cells < 0: for the current device's CU count);
+ * g2048_dweight_jobs is g2048_dweight_jobs_tiled with big_cells = -1.  The partials do not depend on the plan. */
 #define G2048_DWG_MAX_JOBS 16
 typedef struct {
     const void *dy; const void *x; void *parts; float *colsum;
@@ -474,6 +481,8 @@ typedef struct {
     int32_t N, K, slices, parts_f32;
 } g2048_dwg_job;
 int g2048_dweight_jobs(const g2048_dwg_job *jobs, int n_jobs, void *stream);
+int g2048_dweight_jobs_tiled(const g2048_dwg_job *jobs, int n_jobs, int big_cells, void *stream);
+int g2048_dweight_jobs_plan(const g2048_dwg_job *jobs, int n_jobs, int big_cells, int cus, int32_t *n_big);
 
 /* ---- policy network (update): Linear for tall-skinny activations ------------------------------------------ */
 
