@@ -1,7 +1,8 @@
 """ctypes binding of libg2048.so (C ABI: include/g2048.h).
 
 This is the only place the Python host side touches native code.  There is no CPU fallback: if the
-library is missing, or a tensor is not on a HIP device, the call raises.
+library is missing, or a tensor is not on a HIP device, the call raises.  Argument types, structs and
+constants are read from the header itself (``_abi.py``); this module holds the wrappers only.
 """
 from __future__ import annotations
 
@@ -11,109 +12,23 @@ import os
 import numpy as np
 import torch
 
-RNG_LEGACY = 0
-RNG_PARTITIONABLE = 1
-POLICY_DRUL = 0
-POLICY_RANDOM = 1
-MAX_FUSED_STEPS = 128
+from ._abi import NativeError, read as _read_header
 
 _PKG_ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", ".."))
 LIB_PATH = os.environ.get("G2048_LIB", os.path.join(_PKG_ROOT, "lib", "libg2048.so"))
+HEADER_PATH = os.path.join(os.path.dirname(_PKG_ROOT), "include", "g2048.h")
 
-_u32, _i32, _i64, _vp, _dbl = C.c_uint32, C.c_int, C.c_int64, C.c_void_p, C.c_double
+# include/g2048.h, read once per process: name -> (restype, argtypes), C struct name -> ctypes.Structure, G2048_NAME -> int
+PROTOTYPES, STRUCTS, CONSTANTS = _read_header(HEADER_PATH)
+SIGNATURES = {name: argtypes for name, (_, argtypes) in PROTOTYPES.items()}
 
-# name -> argtypes; every entry point declared in include/g2048.h
-SIGNATURES = {
-    "g2048_abi_version": [],
-    "g2048_split": [_u32, _u32, _vp, _i64, _i32, _vp],
-    "g2048_chain_keys": [_vp, _vp, _i64, _i32],
-    "g2048_init": [_vp, _vp, _vp, _vp, _i64, _i32, _vp],
-    "g2048_step": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
-    "g2048_observe": [_vp, _vp, _i64, _vp],
-    "g2048_act_drul": [_vp, _vp, _i64, _vp],
-    "g2048_act_random": [_vp, _vp, _vp, _vp, _i64, _i32, _vp],
-    "g2048_act_logits": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _vp],
-    "g2048_reset_fused": [_u32, _u32, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp],
-    "g2048_rollout_fused": [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64,
-                            _i32, _i32, _i32, _vp, _vp],
-    "g2048_policy_step": [_u32, _u32, _u32, _u32, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
-                          _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp],
-    "g2048_policy_step_autoreset": [_u32, _u32, _u32, _u32, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                    _i64, _i64, _i64, _i32, _vp],
-    "g2048_reset_key": [_u32, _u32, _vp],
-    "g2048_gae_tb": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _dbl, _dbl, _vp],
-    "g2048_gae_tb_boot": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _dbl, _dbl, _vp],
-    "g2048_gae_flat": [_vp, _vp, _vp, _vp, _vp, _i64, _dbl, _dbl, _vp],
-    "g2048_compact": [_vp] * 18 + [_i64, _i64, _vp],
-    "g2048_policy_encoder_workspace_bytes": [_i64],
-    "g2048_policy_encoder": [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp],
-    "g2048_policy_encoder_mean": [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp],
-    "g2048_f32split_pack": [_vp, _i32, _i32, C.c_float, _vp, _vp],
-    "g2048_f32split_gemm": [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp],
-    "g2048_attn_fwd_f32": [_vp, _vp, _i64, _i32, C.c_float, _vp],
-    "g2048_embed_ln_f32": [_vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _i64, _vp],
-    "g2048_lookahead_expand": [_vp, _i64, _vp, _vp, _vp, _vp],
-    "g2048_lookahead_children": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
-    "g2048_lookahead_reduce": [_vp, _vp, _vp, _vp, _vp, _dbl, _i64, _i64, _vp, _vp],
-    "g2048_lookahead_dedup": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
-    "g2048_lookahead_backup": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
-    "g2048_attn_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, C.c_float,
-                       C.c_float, C.c_uint64, _vp, _vp],
-    "g2048_attn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
-                       C.c_float, C.c_float, C.c_uint64, _vp, _vp],
-    "g2048_add_ln_fwd": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, C.c_float, C.c_float, C.c_uint64, _vp, _vp],
-    "g2048_ppo_loss": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, C.c_float, C.c_float, C.c_float, _vp, _vp, _vp,
-                       _vp, _vp, _vp, _vp],
-    "g2048_linear_bf16": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _vp],
-    "g2048_ffn_mask_bytes": [_i64, _i32],
-    "g2048_linear_relu_dropout_bf16": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32, C.c_float, C.c_uint64, _vp, _vp, _vp],
-    "g2048_linear_mask_bwd_workspace_floats": [_i64, _i32],
-    "g2048_linear_mask_bwd_bf16": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, C.c_float, _vp],
-    "g2048_embed_fwd": [_vp, _vp, C.c_int, _vp, _vp, _vp, _i64, C.c_float, C.c_uint64, _vp, _vp],
-    "g2048_embed_ln_fwd": [_vp, _vp, C.c_int, _vp, _vp, _vp, _i64, C.c_float, C.c_uint64, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp],
-    "g2048_embed_bwd_workspace_floats": [_i64],
-    "g2048_embed_bwd": [_vp, _vp, _vp, _vp, _i64, C.c_float, C.c_uint64, _vp, _vp],
-    "g2048_gather_minibatch": [_vp, _i64, _i64] + [_vp] * 13,
-    "g2048_colsum_workspace_floats": [_i64, _i32],
-    "g2048_colsum": [_vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp],
-    "g2048_colsum_partial_rows": [_i64, _i32],
-    "g2048_linear_mask_bwd_partial_rows": [_i64, _i32],
-    "g2048_reduce_jobs": [_vp, _i32, _vp],
-    "g2048_linear_add_ln_fwd": [_vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, C.c_float, C.c_float,
-                                C.c_uint64, _vp, _vp],
-    "g2048_linear_add_ln_bwd_partial_rows": [_i64],
-    "g2048_linear_add_ln_bwd": [_vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
-                                C.c_float, C.c_uint64, _vp, _vp],
-    "g2048_mlp_embed_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _vp],
-    "g2048_gemm_jobs": [_vp, _i32, _i64, _vp],
-    "g2048_mlp_out_fwd": [_vp, _vp, _vp, _vp, _i64, _vp],
-    "g2048_mlp_out_bwd_partial_rows": [_i64],
-    "g2048_mlp_out_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
-    "g2048_add_ln_bwd_workspace_floats": [_i64],
-    "g2048_add_ln_bwd": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, C.c_float, C.c_uint64, _vp,
-                         _i32, _vp],
-    "g2048_relu_dropout_fwd": [_vp, _vp, _i64, _i32, C.c_float, C.c_uint64, _vp, _vp],
-    "g2048_relu_dropout_bwd_workspace_floats": [_i64, _i32],
-    "g2048_relu_dropout_bwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _vp],
-    "g2048_cls_tail_fwd": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, C.c_float, C.c_float, C.c_uint64, _vp, _vp],
-    "g2048_cls_tail_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, C.c_float, C.c_uint64, _vp, _vp],
-    "g2048_dweight_t": [_vp, _i32, _i64, _i64, _i32, _vp],
-    "g2048_dweight_bf16": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp],
-    "g2048_dweight_jobs": [_vp, _i32, _vp],
-    "g2048_dweight_jobs_tiled": [_vp, _i32, _i32, _vp],
-    "g2048_dweight_jobs_plan": [_vp, _i32, _i32, _i32, _vp],
-    "g2048_opt_workspace_floats": [_i32],
-    "g2048_opt_step": [_vp, _i32, _vp, _vp, _vp, _vp, _i32, C.c_float, _vp, _i32, _vp, _vp, C.c_float, C.c_float, _i32, _vp, _vp, _vp],
-    "g2048_lamb_workspace_floats": [_i32],
-    "g2048_lamb_step": [_vp, _i32, _vp, _vp, _vp, _vp, _i32, C.c_float, C.c_float, _vp, _i32, _vp, _vp, C.c_float, C.c_float, _i32, _vp,
-                        _vp, _vp],
-}
+RNG_LEGACY, RNG_PARTITIONABLE = CONSTANTS["G2048_RNG_LEGACY"], CONSTANTS["G2048_RNG_PARTITIONABLE"]
+POLICY_DRUL, POLICY_RANDOM = CONSTANTS["G2048_POLICY_DRUL"], CONSTANTS["G2048_POLICY_RANDOM"]
+MAX_FUSED_STEPS = CONSTANTS["G2048_MAX_FUSED_STEPS"]
+
+_i32, _i64, _vp = C.c_int, C.c_int64, C.c_void_p
 
 _lib = None
-
-
-class NativeError(RuntimeError):
-    pass
 
 
 def load() -> C.CDLL:
@@ -127,11 +42,10 @@ def load() -> C.CDLL:
                 "There is no CPU fallback for the 2048 rollout engine."
             )
         lib = C.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
+        for name, (restype, argtypes) in PROTOTYPES.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
-            fn.argtypes = argtypes
-            fn.restype = C.c_int64 if name.endswith(("_workspace_floats", "_workspace_bytes", "_partial_rows", "_mask_bytes")) else C.c_int
-        if lib.g2048_abi_version() != 4:
+            fn.restype, fn.argtypes = restype, argtypes
+        if lib.g2048_abi_version() != CONSTANTS["G2048_ABI_VERSION"]:
             raise NativeError("libg2048.so ABI version mismatch")
         _lib = lib
     return _lib
@@ -361,7 +275,8 @@ def policy_encoder_mean(boards, embed_table, cls_token, weights_bf16, params_f32
         _stream()), "g2048_policy_encoder_mean")
 
 
-F32SPLIT_BIAS, F32SPLIT_BIAS_RELU, F32SPLIT_ADD_LN, F32SPLIT_ADD = 0, 1, 2, 3
+F32SPLIT_BIAS, F32SPLIT_BIAS_RELU = CONSTANTS["G2048_F32SPLIT_BIAS"], CONSTANTS["G2048_F32SPLIT_BIAS_RELU"]
+F32SPLIT_ADD_LN, F32SPLIT_ADD = CONSTANTS["G2048_F32SPLIT_ADD_LN"], CONSTANTS["G2048_F32SPLIT_ADD"]
 
 
 def f32split_pack(w, scale: float, packed):
@@ -560,12 +475,8 @@ def linear_add_ln_bwd(dy2, wt_packed, xn_ptr: int, x_row_stride: int, g_x, mean,
 
 
 # ---- MLP policy (configs[1]): csrc/g2048_mlp.hip ---------------------------------------------------------------------------------
-GEMM_MAX_JOBS = 8
-
-
-class GemmJob(C.Structure):
-    _fields_ = [("x", _vp * 2), ("ldx", _i64 * 2), ("w", _vp * 2), ("ldw", _i64 * 2), ("k", _i32 * 2), ("bias", _vp), ("act", _vp),
-                ("ldact", _i64), ("y", _vp), ("ldy", _i64), ("N", _i32), ("relu", _i32)]
+GEMM_MAX_JOBS = CONSTANTS["G2048_GEMM_MAX_JOBS"]
+GemmJob = STRUCTS["g2048_gemm_job"]
 
 
 def _bf16_rows(t: torch.Tensor, name: str):
@@ -654,7 +565,7 @@ def relu_dropout_bwd(dy, y, dx, dbias, p_drop: float):
     return ws.view(-1, F) if dbias is None else None
 
 
-COLSUM_MAX_GROUPS = 512
+COLSUM_MAX_GROUPS = CONSTANTS["G2048_COLSUM_MAX_GROUPS"]
 
 
 def colsum(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -686,15 +597,13 @@ def colsum_partial(x: torch.Tensor) -> torch.Tensor:
     return ws[:rows * N].view(rows, N)
 
 
-class ReduceJob(C.Structure):  # g2048_reduce_job
-    _fields_ = [("src", _vp), ("dst", _vp), ("part_stride", _i64), ("n", C.c_int32), ("parts", C.c_int32),
-                ("src_bf16", C.c_int32), ("transpose_rows", C.c_int32)]
+ReduceJob = STRUCTS["g2048_reduce_job"]
 
 
 def reduce_jobs(jobs):
     """jobs: list of (src tensor whose first element is part 0 / column 0, dst f32 tensor, part_stride, n, parts[,
     transpose_rows]): dst[c] = sum_p src[p * part_stride + c] (transpose_rows R: the [R][n / R] sum stored as [n / R][R]); all
-    of them in one launch (per 64)."""
+    of them in one launch (per G2048_REDUCE_MAX_JOBS; the entry point splits longer lists itself)."""
     if not jobs:
         return
     recs = []
@@ -854,21 +763,9 @@ def embed_bwd(boards, dx0, dwt_dcls, p_drop: float = 0.0, seed: int = 0, seed_st
     return ws.view(-1, 32 * 256) if dwt_dcls is None else None
 
 
-OPT_CHUNK = 2048  # G2048_OPT_CHUNK
-OPT_MAX_GROUPS = 4  # G2048_OPT_MAX_GROUPS
-
-
-class OptChunk(C.Structure):  # g2048_opt_chunk
-    _fields_ = [("param", _vp), ("offset", _i64), ("n", C.c_int32), ("group", C.c_int32), ("shadow", _vp), ("shadow_t", _vp),
-                ("shadow_p", _vp), ("shadow_tp", _vp), ("e0", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
-                ("reserved", C.c_int32)]
-
-
+OPT_CHUNK, OPT_MAX_GROUPS = CONSTANTS["G2048_OPT_CHUNK"], CONSTANTS["G2048_OPT_MAX_GROUPS"]
+OptChunk, OptGroup, LambGroup = STRUCTS["g2048_opt_chunk"], STRUCTS["g2048_opt_group"], STRUCTS["g2048_lamb_group"]
 OPT_CHUNK_BYTES = C.sizeof(OptChunk)
-
-
-class OptGroup(C.Structure):  # g2048_opt_group
-    _fields_ = [("lr", _dbl), ("beta1", _dbl), ("beta2", _dbl), ("eps", _dbl), ("weight_decay", _dbl)]
 
 
 def opt_chunk_table(params, offsets, groups, device, shadows=None) -> torch.Tensor:
@@ -904,7 +801,7 @@ def opt_chunk_table(params, offsets, groups, device, shadows=None) -> torch.Tens
 
 
 def opt_workspace(n_chunks: int, device) -> torch.Tensor:
-    """Zeroed workspace for g2048_opt_step (partials + the completion counter the kernel keeps at zero)."""
+    """Zeroed workspace for g2048_opt_step (one partial sum per chunk, then the per-group constants)."""
     return torch.zeros(load().g2048_opt_workspace_floats(n_chunks), dtype=f32, device=device)
 
 
@@ -923,11 +820,6 @@ def opt_step(table, n_chunks: int, grads, exp_avg, exp_avg_sq, groups, max_grad_
         _dev(growth_tracker, torch.int32, 1, "growth_tracker", optional=True), float(growth), float(backoff),
         int(growth_interval), _dev(workspace, f32, None, "workspace"), _dev(info, f32, 2, "info", optional=True), _stream()),
         "g2048_opt_step")
-
-
-class LambGroup(C.Structure):  # g2048_lamb_group
-    _fields_ = [("lr", _dbl), ("beta1", _dbl), ("beta2", _dbl), ("beta3", _dbl), ("eps", _dbl), ("weight_decay", _dbl),
-                ("bias_correction", C.c_int32), ("adapt", C.c_int32), ("trust_clip", C.c_int32), ("reserved", C.c_int32)]
 
 
 def lamb_workspace(n_chunks: int, device) -> torch.Tensor:
@@ -974,8 +866,9 @@ def gather_minibatch(idx, boards, actions, masks, logp, adv, ret, out=None):
 # ---------------------------------------------------------------------------------------------------------------------
 # the 2048-row tail of the update (csrc/g2048_tail.hip)
 # ---------------------------------------------------------------------------------------------------------------------
-TAIL_MASK_TILES = 96
-DW_MAX_JOBS = 16
+TAIL_MASK_TILES, DW_MAX_JOBS = CONSTANTS["G2048_TAIL_MASK_TILES"], CONSTANTS["G2048_DW_MAX_JOBS"]
+TailWeights, TailWeightsT = STRUCTS["g2048_tail_weights"], STRUCTS["g2048_tail_weights_t"]
+TailSaved, TailGrads, DwJob = STRUCTS["g2048_tail_saved"], STRUCTS["g2048_tail_grads"], STRUCTS["g2048_dw_job"]
 
 
 def pack_fragments(x: torch.Tensor) -> torch.Tensor:
@@ -987,28 +880,6 @@ def pack_fragments(x: torch.Tensor) -> torch.Tensor:
 def unpack_fragments(flat: torch.Tensor, rows: int, cols: int) -> torch.Tensor:
     """Inverse of ``pack_fragments``: flat packed tensor -> row-major [rows, cols]."""
     return flat.reshape(rows // 32, cols // 16, 2, 32, 8).permute(0, 3, 1, 2, 4).reshape(rows, cols)
-
-
-class TailWeights(C.Structure):
-    _fields_ = [(n, _vp) for n in ("wo", "w1", "w2", "a1", "a2", "a3", "c1", "c2", "c3", "bo", "b1", "b2", "ab1", "ab2", "cb1", "cb2",
-                                   "ln_g", "ln_b")]
-
-
-class TailWeightsT(C.Structure):
-    _fields_ = [(n, _vp) for n in ("woT", "w1T", "w2T", "a1T", "a2T", "a3", "c1T", "c2T", "c3", "ln_g")]
-
-
-class TailSaved(C.Structure):
-    _fields_ = [(n, _vp) for n in ("x_mid", "mean", "rstd", "masks", "oT", "h2T", "uT", "featsT", "a1T", "a2T", "c1T", "c2T")] \
-        + [("ld", _i64)]
-
-
-class TailGrads(C.Structure):
-    _fields_ = [(n, _vp) for n in ("daoT", "dzT", "df2T", "da1T", "da2T", "dlT", "dc1T", "dc2T", "dvT", "ln_partial")]
-
-
-class DwJob(C.Structure):
-    _fields_ = [("dyT", _vp), ("xT", _vp), ("dw", _vp), ("db", _vp), ("N", C.c_int32), ("K", C.c_int32)]
 
 
 _TAIL_SAVED_ROWS = dict(oT=256, h2T=256, uT=1024, featsT=256, a1T=512, a2T=512, c1T=512, c2T=512)
@@ -1124,12 +995,8 @@ def dweight_parts(dy2: torch.Tensor, x2: torch.Tensor, slices: int, out: torch.T
     return (out, cs) if colsum else out
 
 
-class DwgJob(C.Structure):
-    _fields_ = [("dy", _vp), ("x", _vp), ("parts", _vp), ("colsum", _vp), ("lddy", _i64), ("ldx", _i64), ("T", _i64),
-                ("N", _i32), ("K", _i32), ("slices", _i32), ("parts_f32", _i32)]
-
-
-DWG_MAX_JOBS = 16
+DwgJob = STRUCTS["g2048_dwg_job"]
+DWG_MAX_JOBS = CONSTANTS["G2048_DWG_MAX_JOBS"]
 
 
 def dweight_jobs_plan(shapes, big_cells: int = -1, cus: int = 0):
