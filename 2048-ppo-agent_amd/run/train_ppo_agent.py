@@ -46,6 +46,9 @@ def main():
     ap.add_argument("--eval-episodes", type=int, default=0, help="greedy masked evaluation after training")
     ap.add_argument("--eval-lookahead", type=int, default=0,
                     help="1: the evaluation plays one-ply expectimax over the critic instead of the actor's argmax")
+    ap.add_argument("--symmetry", default=None, choices=["none", "canonical"],
+                    help="canonical: the policy sees every board in its canonical dihedral view, in training and in the evaluation "
+                         "(default: G2048_SYMMETRY, else none)")
     ap.add_argument("overrides", nargs="*")
     args = ap.parse_args()
     cfg = load_config(args.config, args.overrides)
@@ -79,7 +82,7 @@ def main():
         value_loss_coef=t["value_loss_coef"], entropy_coef=t["entropy_coef"], max_grad_norm=t["max_grad_norm"],
         target_kl=t["target_kl"], use_action_mask=t["use_action_mask"], device=device,
         mixed_precision=t["mixed_precision"], max_samples_per_epoch=t["max_samples_per_epoch"],
-        shuffle_on_reset=t["shuffle_on_reset"], rollout_amp=t.get("rollout_amp"))  # None: bf16 rollout when mixed_precision is bfloat16 (G2048_ROLLOUT_FP32=1: fp32)
+        shuffle_on_reset=t["shuffle_on_reset"], rollout_amp=t.get("rollout_amp"), symmetry=args.symmetry)  # None: bf16 rollout when mixed_precision is bfloat16 (G2048_ROLLOUT_FP32=1: fp32)
     if t.get("resume_from_checkpoint"):
         if not os.path.exists(t["resume_from_checkpoint"]):
             raise FileNotFoundError(f"Checkpoint file not found: {t['resume_from_checkpoint']}")
@@ -92,7 +95,9 @@ def main():
         tail = trainer.episode_rewards[-100:]
         logger.info("Final mean episode reward (last 100 episodes): %.2f", sum(tail) / len(tail))
     if args.eval_episodes and trainer.rank == 0:
-        print(json.dumps(evaluate_agent(agent, device, args.eval_episodes, lookahead=args.eval_lookahead, gamma=t["gamma"])))
+        ev = evaluate_agent(agent, device, args.eval_episodes, lookahead=args.eval_lookahead, gamma=t["gamma"],
+                            symmetry=trainer.symmetry)
+        print(json.dumps(dict(ev, symmetry=trainer.symmetry)))
     if world > 1:
         dist.destroy_process_group()
 

@@ -50,6 +50,9 @@ def main():
     ap.add_argument("--eval-lookahead", type=int, default=0,
                     help="1 / 2: every evaluation point also plays one- / two-ply expectimax over the critic on the same seeds (key 'lookahead')")
     ap.add_argument("--eval-episodes", type=int, default=1000, help="episodes per evaluation (a two-ply evaluation can be sized)")
+    ap.add_argument("--symmetry", default=None, choices=["none", "canonical"],
+                    help="canonical: the policy sees every board in its canonical dihedral view, in training and in every evaluation "
+                         "(default: G2048_SYMMETRY, else none)")
     ap.add_argument("--save-agent", default=None, help="write the final agent's state_dict here (tools/probe_lookahead.py reads it)")
     a = ap.parse_args()
 
@@ -64,17 +67,17 @@ def main():
     agent = PPOAgent(**MODEL)
     tr = PPOTrainer(agent, BatchRunner(a.seed, device=dev), RolloutBuffer(31, 16, 4), OPTIM, max_steps=500000, device=dev,
                     rollout_amp=True, log_dir="/tmp/g2048_train_to_2048", rollout_mode=a.mode, rollout_horizon=a.horizon,
-                    **TRAINER)
+                    symmetry=a.symmetry, **TRAINER)
 
     def evaluate(minutes):
-        ev = evaluate_agent(agent, dev, a.eval_episodes) if rank == 0 else None
+        ev = evaluate_agent(agent, dev, a.eval_episodes, symmetry=tr.symmetry) if rank == 0 else None
         if ev is not None and a.eval_lookahead:
             # the same episodes' seeds, the same weights; the greedy figures keep their keys (earlier result files stay comparable)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             # depth 2 is ExpectimaxActionFunction (the one-ply class keeps depth=1 only); any other depth raises as before
             search = dict(expectimax=2) if a.eval_lookahead == 2 else dict(lookahead=a.eval_lookahead)
-            la = evaluate_agent(agent, dev, a.eval_episodes, gamma=TRAINER["gamma"], **search)
+            la = evaluate_agent(agent, dev, a.eval_episodes, gamma=TRAINER["gamma"], symmetry=tr.symmetry, **search)
             torch.cuda.synchronize()
             la.update(depth=a.eval_lookahead, gamma=TRAINER["gamma"], eval_seconds=round(time.perf_counter() - t0, 1))
             ev["lookahead"] = la
@@ -135,7 +138,7 @@ def main():
     if rank == 0:
         res = {"config": "BASELINE.json configs[4] protocol" + ("" if world * 131072 == a.envs else
                          f" at {a.envs} envs on {world} GPU(s) (the 1 M-env / 8-GPU size needs an 8-GPU node)"),
-               "envs": a.envs, "n_gpus": world, "rollout_mode": a.mode, "train_minutes": round(train_s / 60, 2),
+               "envs": a.envs, "n_gpus": world, "rollout_mode": a.mode, "symmetry": tr.symmetry, "train_minutes": round(train_s / 60, 2),
                "timesteps": tr.total_timesteps, "env_steps_per_sec_training": round(tr.total_timesteps / max(train_s, 1e-9), 1),
                "first_2048_tile": first_2048, "evals": evals, "iterations": log,
                "baselines_mean_max_tile": {"random": 109.17, "drul": 189.44, "reference_ppo_readme": 383}}

@@ -377,6 +377,32 @@ def lookahead_backup(reward, nchild, rep, e, v1):
            "g2048_lookahead_backup")
 
 
+def sym_canon(boards, out_boards=None, actions=None, masks=None, frame=None, out_actions=None, out_masks=None):
+    """boards u8 [B,16] -> out_boards = the canonical view of every board, frame u8 [B] = which of the 8 views it is; actions /
+    masks u8 [B] (optional) turned into that view.  An output left None is written over its input (the in-place pass over a
+    rollout buffer); ``frame`` left None is not written."""
+    B = boards.numel() // 16
+    out_boards = boards if out_boards is None else out_boards
+    out_actions = actions if out_actions is None else out_actions
+    out_masks = masks if out_masks is None else out_masks
+    _check(load().g2048_sym_canon(_dev(boards, u8, 16 * B, "boards"), _dev(actions, u8, B, "actions", optional=True),
+                                  _dev(masks, u8, B, "masks", optional=True), B, _dev(out_boards, u8, 16 * B, "out_boards"),
+                                  _dev(out_actions, u8, B, "out_actions", optional=True),
+                                  _dev(out_masks, u8, B, "out_masks", optional=True), _dev(frame, u8, B, "frame", optional=True),
+                                  _stream()),
+           "g2048_sym_canon")
+
+
+def sym_logits(logits, frame, out=None):
+    """logits f32 [B,4] in the canonical frame -> out[b][a] = logits[b][sigma_frame[b](a)], the env's frame (in place when
+    ``out`` is None); the bit patterns are moved."""
+    B = frame.numel()
+    out = logits if out is None else out
+    _check(load().g2048_sym_logits(_dev(logits, f32, 4 * B, "logits"), _dev(frame, u8, B, "frame"), B, _dev(out, f32, 4 * B, "out"),
+                                   _stream()),
+           "g2048_sym_logits")
+
+
 def attn_fwd(q_ptr: int, k_ptr: int, v_ptr: int, o, lse, B: int, H: int, Sq: int, strides, scale: float, p_drop: float,
              seed: int, seed_state: int = 0):
     """q/k/v: raw device addresses inside bf16 tensors the caller keeps alive; strides = (q_sb, q_ss, k_sb, k_ss,

@@ -4,4 +4,4 @@ from .lookahead import LookaheadActionFunction
 from .ppo_agent import MLPAgent, PPOAgent
 from .ppo_trainer import PPOTrainer
 from .rollout_buffer import RolloutBuffer
-from .torch_action_wrapper import TorchActionFunction
+from .torch_action_wrapper import TorchActionFunction, resolve_symmetry

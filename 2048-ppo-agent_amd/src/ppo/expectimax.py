@@ -42,17 +42,18 @@ class ExpectimaxActionFunction(LookaheadActionFunction):
     afterstate's children.  ``max_children``: rows per value-forward call AND level-1 children per slice of roots (whole boards;
     a board has at most 120, hence ``max_children >= 120``): the largest input stays bounded in memory and inside the int32
     offsets.  ``last_children`` is the number of value-forward rows of the latest call, ``last_children_full`` that number without
-    dedup (both from sums the lock-step reads back anyway)."""
+    dedup (both from sums the lock-step reads back anyway).  ``symmetry``: as in the parent (the value forward sees canonical
+    boards; the dedup still compares afterstates as they lie)."""
 
     def __init__(self, agent, plies: int = 2, gamma: float = 0.99, dedup: bool = True, max_children: int = 1 << 18,
                  device: torch.device = torch.device("cpu"), amp_dtype: Optional[torch.dtype] = None, sync_every: int = 8,
-                 rng_mode=None, use_fused: Optional[bool] = None):
+                 rng_mode=None, use_fused: Optional[bool] = None, symmetry: Optional[str] = None):
         if plies not in (1, 2):
             raise ValueError(f"ExpectimaxActionFunction: plies must be 1 or 2, got plies={plies!r}")
         if plies == 2 and int(max_children) < MAX_CHILDREN_PER_BOARD:
             raise ValueError(f"max_children must hold one board's level-1 children (>= {MAX_CHILDREN_PER_BOARD})")
         super().__init__(agent, gamma=gamma, depth=1, max_children=max_children, device=device, amp_dtype=amp_dtype,
-                         sync_every=sync_every, rng_mode=rng_mode, use_fused=use_fused)
+                         sync_every=sync_every, rng_mode=rng_mode, use_fused=use_fused, symmetry=symmetry)
         self.plies = int(plies)
         self.dedup = bool(dedup)
         self.last_children_full = 0

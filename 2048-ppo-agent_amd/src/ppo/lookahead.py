@@ -35,24 +35,29 @@ class LookaheadActionFunction(TorchActionFunction):
     The value forward is the agent's existing one: ``FusedPolicy.__call__`` for a bf16 default-shape PPOAgent of either
     reduction, ``TorchActionFunction._forward`` otherwise; the children's logits are discarded.  A function kept across
     optimiser steps sees the new weights (the fused pack is refreshed when stale, the module forward reads the parameters).
+    ``symmetry``: as in ``TorchActionFunction``; use the mode the critic was trained in.
     """
 
     def __init__(self, agent, gamma: float = 0.99, depth: int = 1, max_children: int = 1 << 18,
                  device: torch.device = torch.device("cpu"), amp_dtype: Optional[torch.dtype] = None, sync_every: int = 8,
-                 rng_mode=None, use_fused: Optional[bool] = None):
+                 rng_mode=None, use_fused: Optional[bool] = None, symmetry: Optional[str] = None):
         if depth != 1:
             raise ValueError(f"LookaheadActionFunction: only depth=1 is implemented, got depth={depth!r}")
         if int(max_children) <= 0:
             raise ValueError("max_children must be a positive number of rows")
         super().__init__(agent, use_mask=True, sample_actions=False, device=device, amp_dtype=amp_dtype,
-                         sync_every=sync_every, rng_mode=rng_mode, use_fused=use_fused)
+                         sync_every=sync_every, rng_mode=rng_mode, use_fused=use_fused, symmetry=symmetry)
         self.gamma = float(gamma)
         self.depth = 1
         self.max_children = int(max_children)
         self.last_children = 0  # N of the latest policy_fn call (probes and tests read it; no extra synchronisation)
 
     def _values(self, rows: torch.Tensor) -> torch.Tensor:
-        """The agent's critic on packed boards u8 [n, 16] -> f32 [n]."""
+        """The agent's critic on packed boards u8 [n, 16] -> f32 [n].  With ``symmetry="canonical"`` the rows are turned into their
+        canonical views first; nothing is mapped back (values are invariant, and ``q`` is in the env's frame because the
+        expansion is)."""
+        if self.symmetry == "canonical":
+            rows = self._canonical(rows, with_frame=False)[0]
         agent_dev = next(self.agent.parameters()).device
         if self._fused is not None and rows.device == agent_dev:
             return self._fused(rows)[1]

@@ -27,7 +27,7 @@ from ..optim import configure_bert_optimizers
 from ..runs.batch_runner import BatchRunner
 from .data_loader import DeviceBatches, PPODataset
 from .rollout_buffer import RolloutBuffer
-from .torch_action_wrapper import TorchActionFunction
+from .torch_action_wrapper import TorchActionFunction, resolve_symmetry
 from . import torch_compat
 from .capture import capture as capture_graph
 from .hip_ops import Bf16Shadow, GradSink, grad_sink, graph_seed_state
@@ -219,7 +219,12 @@ class PPOTrainer:
                  rollout_amp: Optional[bool] = None,
                  log_dir: str = "logs", use_hip_graph: Optional[bool] = None, rollout_mode: Optional[str] = None,
                  rollout_horizon: Optional[int] = None, allreduce_dtype: Optional[str] = None,
-                 allreduce_in_graph: Optional[bool] = None, fp32_native: Optional[bool] = None):
+                 allreduce_in_graph: Optional[bool] = None, fp32_native: Optional[bool] = None,
+                 symmetry: Optional[str] = None):
+        # "canonical": rollouts run behind TorchActionFunction(symmetry="canonical") and the buffer holds what the network saw
+        # (canonical boards, actions and masks in the canonical frame), so the update itself is unchanged and exactly on-policy.
+        # None: G2048_SYMMETRY decides, default "none".  Resolved once: rollout, buffer, metrics and checkpoints agree.
+        self.symmetry = resolve_symmetry(symmetry)
         self.agent = agent.to(device)
         # fp32 rollouts (rollout_amp False) of a default-shape PPOAgent through the split-fp16 kernels (fused_policy.FusedPolicyF32);
         # None: G2048_ROLLOUT_FP32_NATIVE decides (TorchActionFunction), default off
@@ -500,7 +505,7 @@ class PPOTrainer:
         self.rollout_buffer.reset()
         self.agent.eval()
         act = TorchActionFunction(self.agent, use_mask=self.use_action_mask, device=self.device,
-                                  amp_dtype=self.amp_dtype if self.rollout_amp else None, fp32_native=self.fp32_native,
+                                  amp_dtype=self.amp_dtype if self.rollout_amp else None, fp32_native=self.fp32_native, symmetry=self.symmetry,
                                   graph_cache=self._rollout_graphs if getattr(self.agent, "rollout_graph_ok", False) else None)
         self.batch_runner.act_fn = act
         local_b, env0, total = self._shard(batch_size)
@@ -509,11 +514,12 @@ class PPOTrainer:
             self.batch_runner._engine.global_max = self._global_max
         total_episodes = 0
         ep_rew, ep_len = [], []
+        canonical = self.symmetry == "canonical"
         if self.rollout_mode == "fixed_horizon":
             with torch.no_grad():
                 for _ in range(num_batches):
                     traj, last_v = self.batch_runner.collect_fixed(local_b, self.rollout_horizon)
-                    self.rollout_buffer.store_fixed_trajectory(traj, last_v, self.gamma, self.lambda_gae)
+                    self.rollout_buffer.store_fixed_trajectory(traj, last_v, self.gamma, self.lambda_gae, canonical=canonical)
                     lens = traj.finished_episode_lengths()
                     total_episodes += int(lens.numel())
                     ep_len.append(lens)
@@ -528,7 +534,7 @@ class PPOTrainer:
         with torch.no_grad():
             for _ in range(num_batches):
                 traj = self.batch_runner.collect(local_b)
-                self.rollout_buffer.store_trajectory(traj, self.gamma, self.lambda_gae)
+                self.rollout_buffer.store_trajectory(traj, self.gamma, self.lambda_gae, canonical=canonical)
                 total_episodes += traj.B
                 # "episode reward" statistic of the reference: the largest single-step reward of the env's row
                 valid = traj.valid()
@@ -809,6 +815,7 @@ class PPOTrainer:
         # how the minibatches ran: replayed hipGraph (and how many captured layouts) or the eager fallback
         metrics["hip_graph"] = bool(self.use_hip_graph and self._graphs)
         metrics["hip_graphs_captured"] = len(self._graphs)
+        metrics["symmetry"] = self.symmetry
         if self.hip_graph_fallback:
             metrics["hip_graph_fallback"] = self.hip_graph_fallback
         # the rollout forward's own capture (agents with ``rollout_graph_ok``): why it runs eagerly, if it does
@@ -841,6 +848,7 @@ class PPOTrainer:
             "total_timesteps": self.total_timesteps, "total_epochs": self.total_epochs,
             "total_update_steps": self.total_update_steps, "episode_rewards": list(self.episode_rewards),
             "episode_lengths": list(self.episode_lengths), "last_save_timestep": self.last_save_timestep,
+            "symmetry": self.symmetry,
         }
         if self.use_amp and self.scaler is not None:
             ckpt["scaler_state_dict"] = self.scaler.state_dict()
@@ -855,6 +863,10 @@ class PPOTrainer:
         if missing:
             raise ValueError(f"Checkpoint missing required keys: {missing}")
         self.agent.load_state_dict(ckpt["agent_state_dict"])
+        stored = ckpt.get("symmetry", "none")  # (checkpoints from before the mode existed were trained without it)
+        if stored != self.symmetry:
+            logger.warning("Checkpoint was trained with symmetry=%r but this trainer runs symmetry=%r: a network trained on "
+                           "canonical boards is only meaningful behind the same wrapper.", stored, self.symmetry)
         if load_optimizer:
             if self._flat_step is not None:
                 self._flat_step.sync_step_counts()  # (a load that fails keeps the live state: its step count must be current too)

@@ -71,11 +71,14 @@ class RolloutBuffer:
             self.buffer_size += n
 
     # ------------------------------------------------------------------ device interface
-    def store_trajectory(self, traj: Trajectory, gamma: float = None, lambda_gae: float = None) -> int:
+    def store_trajectory(self, traj: Trajectory, gamma: float = None, lambda_gae: float = None, canonical: bool = False) -> int:
         """Compact an engine trajectory into the buffer on the device; returns the number of kept steps.
         With ``gamma``/``lambda_gae`` the raw GAE advantages and returns are computed first, on the step-major [T][B] layout
         where the scan is fully coalesced (``g2048_gae_tb``, one lane per env, bit-identical to the reference's scan over
-        the compacted buffer), and compacted along: PPODataset then skips its own scan."""
+        the compacted buffer), and compacted along: PPODataset then skips its own scan.
+        ``canonical``: the rollout ran behind ``TorchActionFunction(symmetry="canonical")``, so the kept rows are turned into what
+        the network saw: canonical board, action and legal mask in the canonical frame (``g2048_sym_canon``, in place).  Log-probs,
+        values, rewards, GAE columns and terminations do not depend on the frame."""
         if traj.log_probs is None or traj.values is None:
             raise ValueError("PPO needs log_probs and values; this trajectory has none (naive policy?)")
         dev = traj.ep_len.device
@@ -105,15 +108,17 @@ class RolloutBuffer:
                    out["boards"], out["actions"], out["masks"], out["rewards"], out["log_probs"], out["values"],
                    out["terms"], traj.T, traj.B, N, tr_adv=tr_adv, tr_ret=tr_ret, out_adv=out.get("raw_advantages"),
                    out_ret=out.get("raw_returns"))
+        if canonical:
+            nv.sym_canon(out["boards"], actions=out["actions"], masks=out["masks"])
         self._segments.append(("device", out))
         self.buffer_size += N
         return N
 
-    def store_fixed_trajectory(self, traj, last_values: torch.Tensor, gamma: float, lambda_gae: float) -> int:
+    def store_fixed_trajectory(self, traj, last_values: torch.Tensor, gamma: float, lambda_gae: float, canonical: bool = False) -> int:
         """A fixed-horizon trajectory (``FixedTrajectory``: all T x B rows are samples, ``terms`` marks the episode
         boundaries): GAE on the [T][B] layout bootstrapped from ``last_values`` = V(state after the last step)
         (``g2048_gae_tb_boot``), then the rows are taken over as they lie (step-major; copied, because the engine reuses
-        its trajectory workspace)."""
+        its trajectory workspace).  ``canonical``: as in ``store_trajectory``, on the copied rows."""
         T, B = traj.T, traj.B
         adv, ret = torch.empty_like(traj.rewards), torch.empty_like(traj.rewards)
         nv.gae_tb_boot(traj.rewards, traj.values, traj.meta, last_values.to(torch.float32).reshape(-1).contiguous(), adv, ret,
@@ -125,6 +130,8 @@ class RolloutBuffer:
             "log_probs": traj.log_probs.reshape(N).clone(), "values": traj.values.reshape(N).clone(),
             "terms": ((traj.meta >> 6) & 1).reshape(N), "raw_advantages": adv.reshape(N), "raw_returns": ret.reshape(N),
         }
+        if canonical:
+            nv.sym_canon(out["boards"], actions=out["actions"], masks=out["masks"])
         self._segments.append(("device", out))
         self.buffer_size += N
         return N

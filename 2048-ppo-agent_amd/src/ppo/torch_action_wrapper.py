@@ -27,6 +27,19 @@ def resolve_fp32_native(fp32_native=None, environ=None) -> bool:
     return environ.get("G2048_ROLLOUT_FP32_NATIVE", "0").strip().lower() in ("1", "true", "yes", "on")
 
 
+SYMMETRY_MODES = ("none", "canonical")
+
+
+def resolve_symmetry(symmetry=None, environ=None) -> str:
+    """An explicit argument wins; else G2048_SYMMETRY; default "none".  -> "none" | "canonical"; anything else raises."""
+    if symmetry is None:
+        environ = os.environ if environ is None else environ
+        symmetry = environ.get("G2048_SYMMETRY", "none").strip().lower() or "none"
+    if symmetry not in SYMMETRY_MODES:
+        raise ValueError(f"symmetry must be one of {SYMMETRY_MODES} (or None: ask G2048_SYMMETRY), got {symmetry!r}")
+    return symmetry
+
+
 class TorchActionFunction:
     """Wrap an actor-critic ``agent`` as an ``act_fn`` plug-in for BatchRunner.
 
@@ -38,13 +51,19 @@ class TorchActionFunction:
     live-env counter; ``fp32_native`` sends an fp32 rollout (``amp_dtype`` None) of such a PPOAgent on a HIP device through the
     split-fp16 kernels (``fused_policy.FusedPolicyF32``: f32-grade results on the f16 matrix cores) - ``None`` asks
     G2048_ROLLOUT_FP32_NATIVE (default off); anywhere else the switch does nothing and the module forward runs.
+    ``symmetry="canonical"`` (``None`` asks G2048_SYMMETRY, default "none") puts every forward into the canonical frame: the
+    boards are turned into the lexicographically largest of their eight dihedral views (``g2048_sym_canon``), the forward above
+    runs unchanged on those, and the four logits are turned back into the env's frame (``g2048_sym_logits``).  The policy is then
+    exactly equivariant and the value exactly invariant under the symmetries of the board, for one forward; the env, its key
+    stream and the trajectory stay in the env's frame.  Train and evaluate an agent in the same mode.
     Side effect as in the reference: ``agent`` is moved to ``device`` and put in eval mode.
     """
 
     def __init__(self, agent, use_mask: bool = False, sample_actions: bool = True,
                  device: torch.device = torch.device("cpu"), amp_dtype: Optional[torch.dtype] = None,
                  sync_every: int = 8, rng_mode=None, use_fused: Optional[bool] = None, graph_cache: Optional[dict] = None,
-                 fp32_native: Optional[bool] = None):
+                 fp32_native: Optional[bool] = None, symmetry: Optional[str] = None):
+        self.symmetry = resolve_symmetry(symmetry)  # (first: an unknown mode is refused before the agent is touched)
         self.agent = agent.to(device).eval()
         self.use_mask = use_mask
         self.sample_actions = sample_actions
@@ -80,6 +99,31 @@ class TorchActionFunction:
     @torch.no_grad()
     def policy_fn(self, boards: torch.Tensor, masks: torch.Tensor):
         """boards u8 [B, 16], masks u8 [B] or None (unused here) -> (logits f32 [B, 4], values f32 [B])."""
+        if self.symmetry == "canonical":
+            canon, frame = self._canonical(boards)
+            logits, values = self._policy(canon)
+            logits = logits.contiguous()
+            if logits.data_ptr() % 16:  # (a view into a larger tensor: the kernel moves 16-byte rows)
+                logits = logits.clone()
+            if logits.shape[0]:
+                nv.sym_logits(logits, frame)  # in place: nothing keeps the forward's output in the canonical frame
+            return logits, values
+        return self._policy(boards)
+
+    policy_fn.needs_masks = False  # (RolloutEngine.rollout_policy: no per-lock-step gather of the masks for this policy)
+
+    @staticmethod
+    def _canonical(boards: torch.Tensor, with_frame: bool = True):
+        """boards u8 [n, 16] -> (their canonical views (a new tensor), frame u8 [n] or None)."""
+        boards = boards.contiguous()
+        canon = torch.empty_like(boards)
+        frame = torch.empty(boards.shape[0], dtype=torch.uint8, device=boards.device) if with_frame else None
+        if boards.shape[0]:
+            nv.sym_canon(boards, canon, frame=frame)
+        return canon, frame
+
+    def _policy(self, boards: torch.Tensor):
+        """The forward as it is without a symmetry mode: fused kernel, replayed graph or module, whichever applies."""
         agent_dev = next(self.agent.parameters()).device
         if self._fused is not None and boards.device == agent_dev:
             return self._fused(boards)
@@ -88,8 +132,6 @@ class TorchActionFunction:
             if out is not None:
                 return out
         return self._forward(boards, agent_dev)
-
-    policy_fn.needs_masks = False  # (RolloutEngine.rollout_policy: no per-lock-step gather of the masks for this policy)
 
     def _forward(self, boards, agent_dev):
         x = boards if boards.device == agent_dev else boards.to(agent_dev)
@@ -142,9 +184,12 @@ class TorchActionFunction:
         obs_t = torch.as_tensor(np.asarray(obs.cpu() if isinstance(obs, torch.Tensor) else obs))
         batched = obs_t.ndim > 3
         obs_t = obs_t.reshape(-1, BOARD_FLAT_DIM, OBS_DIM).float()
-        agent_dev = next(self.agent.parameters()).device
-        logits, values = self.agent(obs_t.to(agent_dev), None)
         dev = C.device()
+        if self.symmetry == "canonical":  # the one-hot observation is decoded to packed boards and goes down policy_fn
+            logits, values = self.policy_fn(obs_t.argmax(dim=-1).to(torch.uint8).to(dev), None)
+        else:
+            agent_dev = next(self.agent.parameters()).device
+            logits, values = self.agent(obs_t.to(agent_dev), None)
         bits = C.mask_to_bits(mask)
         keys = C.keys_tensor(rng_key)
         n = bits.numel()

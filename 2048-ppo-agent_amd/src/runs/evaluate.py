@@ -43,13 +43,16 @@ def evaluate_max_tile(act_fn: Callable, num_episodes: int = 1000, seed: int = 42
 
 
 def evaluate_agent(agent, device, num_episodes: int = 1000, seed: int = 42, rng_mode=None, lookahead: int = 0,
-                   gamma: float = 0.99, expectimax: int = 0) -> Dict:
+                   gamma: float = 0.99, expectimax: int = 0, symmetry=None) -> Dict:
     """Greedy, masked evaluation of a PPO agent (run/viz_ppo_agent.py:267-300).  ``lookahead=1``: the same protocol (same
     seeds, same env and key stream) played by one-ply expectimax over the agent's critic with discount ``gamma``
     (``LookaheadActionFunction``) instead of the actor's argmax; ``lookahead=0`` is the reference's evaluation.  ``expectimax=2``: the same
     protocol played by two-ply expectimax (``ExpectimaxActionFunction``); it excludes ``lookahead``, whose only depth stays 1, and takes
-    no other value than 0 and 2 (one ply is spelled ``lookahead=1``)."""
-    from ..ppo.torch_action_wrapper import TorchActionFunction
+    no other value than 0 and 2 (one ply is spelled ``lookahead=1``).  ``symmetry``: "none" / "canonical" / None (ask
+    G2048_SYMMETRY), handed to whichever action function is built; evaluate an agent in the mode it was trained in."""
+    from ..ppo.torch_action_wrapper import TorchActionFunction, resolve_symmetry
+
+    symmetry = resolve_symmetry(symmetry)
 
     if lookahead and expectimax:
         raise ValueError("evaluate_agent: lookahead and expectimax are mutually exclusive")
@@ -59,13 +62,13 @@ def evaluate_agent(agent, device, num_episodes: int = 1000, seed: int = 42, rng_
     if expectimax:
         from ..ppo.expectimax import ExpectimaxActionFunction
 
-        fn = ExpectimaxActionFunction(agent, plies=expectimax, gamma=gamma, device=device)
+        fn = ExpectimaxActionFunction(agent, plies=expectimax, gamma=gamma, device=device, symmetry=symmetry)
     elif lookahead:
         from ..ppo.lookahead import LookaheadActionFunction
 
-        fn = LookaheadActionFunction(agent, gamma=gamma, depth=lookahead, device=device)
+        fn = LookaheadActionFunction(agent, gamma=gamma, depth=lookahead, device=device, symmetry=symmetry)
     else:
-        fn = TorchActionFunction(agent, use_mask=True, sample_actions=False, device=device)
+        fn = TorchActionFunction(agent, use_mask=True, sample_actions=False, device=device, symmetry=symmetry)
     try:
         return evaluate_max_tile(fn, num_episodes, seed, rng_mode=rng_mode, device=device)
     finally:

@@ -294,6 +294,32 @@ int g2048_lookahead_dedup(const uint8_t *after, const int32_t *nchild, const int
 int g2048_lookahead_backup(const float *reward, const int32_t *nchild, const int32_t *rep, const float *e, int64_t N1, float *v1,
                            void *stream);
 
+/* ---- canonical frame: the dihedral symmetry of the board around the policy forward ---------------------------------------
+ * (no reference counterpart: the reference's forward, src/ppo/torch_action_wrapper.py:73-102, sees the board as it lies; these
+ * two kernels wrap that forward.)  A position has eight equivalent views g = 4 f + k, f in {0, 1}, k in 0 .. 3:
+ * view_g(board) = np.rot90(T_f(board as 4 x 4), k) flattened row-major, T_1 the transpose, T_0 the identity.  The action that
+ * does in view g what a does in the env's frame (0 left, 1 up, 2 right, 3 down) is sigma_g(a) = ((a ^ f) - k) mod 4:
+ * move(view_g(s), sigma_g(a)) = view_g(move(s, a)) with the same merge score.  canon(s) is the view whose 16 bytes, compared
+ * from cell 0 upward, are lexicographically largest, frame(s) the smallest g that attains it; canon(view_h(s)) = canon(s) for
+ * every h.  The policy pi'(a | s) = pi_net(sigma_g(a) | canon(s)), g = frame(s), is exactly equivariant and its value
+ * exactly invariant, for one forward. */
+
+/* out_boards[b] = canon(boards[b]) (one 16-byte store), frame[b] = frame(boards[b]), out_actions[b] =
+ * sigma_g(actions[b] & 3), out_masks[b]: bit sigma_g(a) = bit a of masks[b], bits 4 .. 7 zero (g = frame(boards[b])).
+ * actions / out_actions and masks / out_masks are optional, null together; frame is optional on its own.  Every output may be
+ * the same pointer as its input (the in-place pass over a rollout buffer); any other overlap is the caller's error.  One lane
+ * per board; rows at or past B are not touched.
+ * G2048_EINVAL: null boards or out_boards, exactly one pointer of an optional pair, B outside 1 .. 2^30, boards or out_boards
+ * not 16-byte aligned. */
+int g2048_sym_canon(const uint8_t *boards, const uint8_t *actions, const uint8_t *masks, int64_t B, uint8_t *out_boards,
+                    uint8_t *out_actions, uint8_t *out_masks, uint8_t *frame, void *stream);
+
+/* out f32[B][4]: out[b][a] = logits[b][sigma_g(a)], g = frame[b] & 7: the canonical-frame logits of the forward back in the
+ * env's frame.  One 16-byte load and one 16-byte store per lane; the f32 bit patterns are moved, not recomputed (NaN payloads
+ * and the sign of zero survive).  out may be logits.
+ * G2048_EINVAL: a null pointer, B outside 1 .. 2^30, logits or out not 16-byte aligned. */
+int g2048_sym_logits(const float *logits, const uint8_t *frame, int64_t B, float *out, void *stream);
+
 /* ---- policy network (update): attention for 17-token sequences ------------------------------------- */
 
 /* softmax(q k^T * scale) v with attention dropout, head_dim 32, Sk = 17 keys, Sq = 17 queries (or 1: the CLS row
