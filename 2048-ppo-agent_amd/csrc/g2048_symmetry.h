@@ -72,4 +72,64 @@ G_DEV u32 sym_canon(Board &bd) {
 // out[a] = in[sigma_g(a)] on four 32-bit patterns (selects: a register array indexed by a lane value would go to scratch)
 G_DEV u32 sym_pick(u32 x, u32 y, u32 z, u32 w, u32 i) { return i == 0 ? x : (i == 1 ? y : (i == 2 ? z : w)); }
 
+// ---- eight-view ensemble (include/g2048.h, "eight-view ensemble") ----------------------------------------------------------------
+// view_g(m), g in 0 .. 7 (the low three bits count).  In the table at the top of the file the view is built from t for
+// g in {1, 3, 4, 6}, byte-reversed for g in {2, 3, 6, 7} and in reversed row order for g in {1, 2, 5, 6}: three bits of g, three
+// rounds of selects (a register array indexed by a lane value would go to scratch).
+G_DEV Board sym_view(const Board &m, u32 g) {
+    Board t = m, hm, ht, out;
+    transpose(t);
+    for (int i = 0; i < 4; ++i) {
+        hm.r[i] = reverse_bytes(m.r[i]);
+        ht.r[i] = reverse_bytes(t.r[i]);
+    }
+    const bool from_t = ((g ^ (g >> 2)) & 1u) != 0, flipped = (g & 2u) != 0, reversed = ((g ^ (g >> 1)) & 1u) != 0;
+    u32 x[4];
+    for (int i = 0; i < 4; ++i) {
+        const u32 plain = from_t ? t.r[i] : m.r[i], turned = from_t ? ht.r[i] : hm.r[i];
+        x[i] = flipped ? turned : plain;
+    }
+    for (int i = 0; i < 4; ++i) out.r[i] = reversed ? x[3 - i] : x[i];
+    return out;
+}
+
+G_DEV u32 float_as_u32(float x) {
+#if G2048_ON_DEVICE
+    return __float_as_uint(x);
+#else
+    u32 b;
+    memcpy(&b, &x, 4);
+    return b;
+#endif
+}
+
+// f32 bit pattern <-> an unsigned key whose order is the total order of the patterns as sign-magnitude numbers:
+// -NaN < -inf < .. < -0 < +0 < .. < +inf < +NaN
+G_DEV u32 sym_sort_key(u32 bits) { return bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
+G_DEV u32 sym_sort_unkey(u32 key) { return key ^ ((key >> 31) ? 0x80000000u : 0xFFFFFFFFu); }
+
+G_DEV void sym_cmpx(u32 &a, u32 &b) {
+    const u32 lo = a < b ? a : b, hi = a < b ? b : a;
+    a = lo;
+    b = hi;
+}
+
+// The mean of eight f32 (as bit patterns, result as a bit pattern) as a function of their MULTISET: sorted by the order above
+// with a fixed 19-compare-exchange network on the integer keys (which, unlike fminf / fmaxf, cannot drop a NaN), added in
+// ascending order, every add rounded on its own, times 0.125 (exact short of underflow).  NaN whenever an addend is NaN or both
+// infinities occur (payload unspecified); equal keys are equal patterns, and -0 / +0 are neighbours in the order, so no
+// permutation of the eight changes a bit of the result.  x[] is left sorted as keys; all indices are constants after unrolling.
+G_DEV u32 sym_sorted_mean8(u32 x[8]) {
+    for (int i = 0; i < 8; ++i) x[i] = sym_sort_key(x[i]);
+    sym_cmpx(x[0], x[2]); sym_cmpx(x[1], x[3]); sym_cmpx(x[4], x[6]); sym_cmpx(x[5], x[7]);
+    sym_cmpx(x[0], x[4]); sym_cmpx(x[1], x[5]); sym_cmpx(x[2], x[6]); sym_cmpx(x[3], x[7]);
+    sym_cmpx(x[0], x[1]); sym_cmpx(x[2], x[3]); sym_cmpx(x[4], x[5]); sym_cmpx(x[6], x[7]);
+    sym_cmpx(x[2], x[4]); sym_cmpx(x[3], x[5]);
+    sym_cmpx(x[1], x[4]); sym_cmpx(x[3], x[6]);
+    sym_cmpx(x[1], x[2]); sym_cmpx(x[3], x[4]); sym_cmpx(x[5], x[6]);
+    float s = u32_as_float(sym_sort_unkey(x[0]));
+    for (int i = 1; i < 8; ++i) s = add_rn(s, u32_as_float(sym_sort_unkey(x[i])));
+    return float_as_u32(mul_rn(s, 0.125f));
+}
+
 }  // namespace g2048

@@ -25,7 +25,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
-from src.ppo import PPOAgent, PPOTrainer, RolloutBuffer  # noqa: E402
+from src.ppo import PPOAgent, PPOTrainer, RolloutBuffer, resolve_symmetry  # noqa: E402
 from src.runs import BatchRunner, evaluate_agent  # noqa: E402
 
 TRAINER = dict(gamma=0.99, lambda_gae=0.95, clip_epsilon=0.2, value_loss_coef=0.5, entropy_coef=0.01, max_grad_norm=0.5,
@@ -53,8 +53,14 @@ def main():
     ap.add_argument("--symmetry", default=None, choices=["none", "canonical"],
                     help="canonical: the policy sees every board in its canonical dihedral view, in training and in every evaluation "
                          "(default: G2048_SYMMETRY, else none)")
+    ap.add_argument("--eval-ensemble", action="store_true",
+                    help="every evaluation point also plays the same seeds with symmetry='ensemble' (the mean over the eight dihedral views): "
+                         "greedy, and the search player of --eval-lookahead when given (key 'ensemble'); not with --symmetry canonical")
     ap.add_argument("--save-agent", default=None, help="write the final agent's state_dict here (tools/probe_lookahead.py reads it)")
     a = ap.parse_args()
+    if a.eval_ensemble and resolve_symmetry(a.symmetry) == "canonical":
+        ap.error("--eval-ensemble averages the eight views of a board; behind the canonical frame they are eight copies of one row "
+                 "(--symmetry canonical / G2048_SYMMETRY=canonical)")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -81,6 +87,22 @@ def main():
             torch.cuda.synchronize()
             la.update(depth=a.eval_lookahead, gamma=TRAINER["gamma"], eval_seconds=round(time.perf_counter() - t0, 1))
             ev["lookahead"] = la
+        if ev is not None and a.eval_ensemble:
+            # the same weights and episode seeds once more, every forward replaced by the mean over the eight views
+            def timed_eval(**search):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = evaluate_agent(agent, dev, a.eval_episodes, gamma=TRAINER["gamma"], symmetry="ensemble", **search)
+                torch.cuda.synchronize()
+                out["eval_seconds"] = round(time.perf_counter() - t0, 1)
+                return out
+
+            ens = timed_eval()
+            if a.eval_lookahead:
+                la = timed_eval(**(dict(expectimax=2) if a.eval_lookahead == 2 else dict(lookahead=a.eval_lookahead)))
+                la.update(depth=a.eval_lookahead, gamma=TRAINER["gamma"])
+                ens["lookahead"] = la
+            ev["ensemble"] = ens
         if world > 1:
             dist.barrier()
         if ev is not None:
@@ -90,6 +112,13 @@ def main():
             if "lookahead" in ev:
                 la = ev["lookahead"]
                 print(f"  lookahead {la['depth']}: mean max tile {la['mean_max_tile']:.1f}  {la['percent']}  ({la['eval_seconds']} s)", flush=True)
+            if "ensemble" in ev:
+                ens = ev["ensemble"]
+                print(f"  ensemble: mean max tile {ens['mean_max_tile']:.1f}  {ens['percent']}  ({ens['eval_seconds']} s)", flush=True)
+                if "lookahead" in ens:
+                    la = ens["lookahead"]
+                    print(f"  ensemble lookahead {la['depth']}: mean max tile {la['mean_max_tile']:.1f}  {la['percent']}  "
+                          f"({la['eval_seconds']} s)", flush=True)
             if a.out:  # the evaluation points so far, should the run be cut short (the full result replaces this file at the end)
                 os.makedirs(os.path.dirname(os.path.abspath(a.out)) or ".", exist_ok=True)
                 json.dump({"partial": True, "evals": evals + [ev]}, open(a.out, "w"), indent=1)

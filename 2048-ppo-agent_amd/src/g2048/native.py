@@ -403,6 +403,26 @@ def sym_logits(logits, frame, out=None):
            "g2048_sym_logits")
 
 
+def sym_views(boards, views):
+    """boards u8 [B,16] -> views u8 [B,8,16] (or [8 B,16]): views[b][g] = view_g(boards[b]), the rows of the ensemble's forward."""
+    B = boards.numel() // 16
+    _check(load().g2048_sym_views(_dev(boards, u8, 16 * B, "boards"), B, _dev(views, u8, 128 * B, "views"), _stream()),
+           "g2048_sym_views")
+
+
+def sym_fold(logits, values, out_logits, out_values):
+    """logits f32 [8 B,4] / values f32 [8 B] of a forward on ``sym_views``' rows -> out_logits f32 [B,4] / out_values f32 [B]: the
+    order-free mean over the eight views, the logits in the env's frame.  Either pair may be None (both of it), not both pairs."""
+    out = out_logits if out_logits is not None else out_values
+    if out is None:
+        raise NativeError("sym_fold: out_logits or out_values required")
+    B = out.numel() // 4 if out_logits is not None else out.numel()
+    _check(load().g2048_sym_fold(_dev(logits, f32, 32 * B, "logits", optional=True), _dev(values, f32, 8 * B, "values", optional=True), B,
+                                 _dev(out_logits, f32, 4 * B, "out_logits", optional=True),
+                                 _dev(out_values, f32, B, "out_values", optional=True), _stream()),
+           "g2048_sym_fold")
+
+
 def attn_fwd(q_ptr: int, k_ptr: int, v_ptr: int, o, lse, B: int, H: int, Sq: int, strides, scale: float, p_drop: float,
              seed: int, seed_state: int = 0):
     """q/k/v: raw device addresses inside bf16 tensors the caller keeps alive; strides = (q_sb, q_ss, k_sb, k_ss,

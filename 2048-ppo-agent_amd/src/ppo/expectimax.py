@@ -43,7 +43,8 @@ class ExpectimaxActionFunction(LookaheadActionFunction):
     a board has at most 120, hence ``max_children >= 120``): the largest input stays bounded in memory and inside the int32
     offsets.  ``last_children`` is the number of value-forward rows of the latest call, ``last_children_full`` that number without
     dedup (both from sums the lock-step reads back anyway).  ``symmetry``: as in the parent (the value forward sees canonical
-    boards; the dedup still compares afterstates as they lie)."""
+    boards, or under "ensemble" all eight views of every child, in chunks of ``max_children // 8`` boards; the dedup still compares
+    afterstates as they lie, and ``last_children`` counts boards)."""
 
     def __init__(self, agent, plies: int = 2, gamma: float = 0.99, dedup: bool = True, max_children: int = 1 << 18,
                  device: torch.device = torch.device("cpu"), amp_dtype: Optional[torch.dtype] = None, sync_every: int = 8,
@@ -136,8 +137,8 @@ class ExpectimaxActionFunction(LookaheadActionFunction):
         terminal2 = torch.empty(N2, dtype=torch.uint8, device=dev)
         values = torch.empty(N2, dtype=torch.float32, device=dev)
         nv.lookahead_children(after2, nuniq, offset2, N2, children2, terminal2)
-        for c0 in range(0, N2, self.max_children):
-            c1 = min(N2, c0 + self.max_children)
+        for c0 in range(0, N2, self._chunk):
+            c1 = min(N2, c0 + self._chunk)
             values[c0:c1] = self._values(children2[c0:c1]).to(torch.float32).reshape(-1)
         e = torch.empty((N1, 4), dtype=torch.float32, device=dev)
         nv.lookahead_reduce(torch.zeros_like(reward2), nuniq, offset2, values, terminal2, self.gamma, N2, e)

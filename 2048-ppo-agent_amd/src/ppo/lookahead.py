@@ -35,7 +35,9 @@ class LookaheadActionFunction(TorchActionFunction):
     The value forward is the agent's existing one: ``FusedPolicy.__call__`` for a bf16 default-shape PPOAgent of either
     reduction, ``TorchActionFunction._forward`` otherwise; the children's logits are discarded.  A function kept across
     optimiser steps sees the new weights (the fused pack is refreshed when stale, the module forward reads the parameters).
-    ``symmetry``: as in ``TorchActionFunction``; use the mode the critic was trained in.
+    ``symmetry``: as in ``TorchActionFunction``; use the mode the critic was trained in, or "ensemble" with any critic: the value
+    of a child is then the mean over its eight views, ``max_children`` still bounds the forward rows per call (a chunk holds
+    ``max(1, max_children // 8)`` boards) and ``last_children`` still counts boards.
     """
 
     def __init__(self, agent, gamma: float = 0.99, depth: int = 1, max_children: int = 1 << 18,
@@ -55,13 +57,21 @@ class LookaheadActionFunction(TorchActionFunction):
     def _values(self, rows: torch.Tensor) -> torch.Tensor:
         """The agent's critic on packed boards u8 [n, 16] -> f32 [n].  With ``symmetry="canonical"`` the rows are turned into their
         canonical views first; nothing is mapped back (values are invariant, and ``q`` is in the env's frame because the
-        expansion is)."""
+        expansion is).  With ``symmetry="ensemble"`` the value forward runs on the eight views of every row and the values are
+        folded (``g2048_sym_fold``, values only): f32 [n] again, invariant under the symmetries of each row."""
+        if self.symmetry == "ensemble":  # (_policy is the forward below: this class never holds a graph cache)
+            return self._ensemble(rows, want_logits=False)[1]
         if self.symmetry == "canonical":
             rows = self._canonical(rows, with_frame=False)[0]
         agent_dev = next(self.agent.parameters()).device
         if self._fused is not None and rows.device == agent_dev:
             return self._fused(rows)[1]
         return self._forward(rows, agent_dev)[1]
+
+    @property
+    def _chunk(self) -> int:
+        """Boards per ``_values`` call: ``max_children`` counts forward rows, and the ensemble makes eight of a board."""
+        return max(1, self.max_children // 8) if self.symmetry == "ensemble" else self.max_children
 
     @torch.no_grad()
     def policy_fn(self, boards: torch.Tensor, masks: torch.Tensor = None):
@@ -79,8 +89,8 @@ class LookaheadActionFunction(TorchActionFunction):
         terminal = torch.empty(N, dtype=torch.uint8, device=dev)
         values = torch.empty(N, dtype=torch.float32, device=dev)
         nv.lookahead_children(after, nchild, offset, N, children, terminal)
-        for c0 in range(0, N, self.max_children):
-            c1 = min(N, c0 + self.max_children)
+        for c0 in range(0, N, self._chunk):
+            c1 = min(N, c0 + self._chunk)
             values[c0:c1] = self._values(children[c0:c1]).to(torch.float32).reshape(-1)
         q = torch.empty((B, 4), dtype=torch.float32, device=dev)
         nv.lookahead_reduce(reward, nchild, offset, values, terminal, self.gamma, N, q)

@@ -225,6 +225,11 @@ class PPOTrainer:
         # (canonical boards, actions and masks in the canonical frame), so the update itself is unchanged and exactly on-policy.
         # None: G2048_SYMMETRY decides, default "none".  Resolved once: rollout, buffer, metrics and checkpoints agree.
         self.symmetry = resolve_symmetry(symmetry)
+        if self.symmetry == "ensemble":  # (also when G2048_SYMMETRY said so: refused before anything is touched)
+            raise ValueError('symmetry="ensemble" is a mode for play (TorchActionFunction, Lookahead/ExpectimaxActionFunction, '
+                             "evaluate_agent), not for training: the update would need eight forwards with gradients per sample, "
+                             "and the log_prob recorded under the ensemble is not what a single-view update recomputes.  Train with "
+                             '"none" or "canonical" and evaluate with symmetry="ensemble".')
         self.agent = agent.to(device)
         # fp32 rollouts (rollout_amp False) of a default-shape PPOAgent through the split-fp16 kernels (fused_policy.FusedPolicyF32);
         # None: G2048_ROLLOUT_FP32_NATIVE decides (TorchActionFunction), default off

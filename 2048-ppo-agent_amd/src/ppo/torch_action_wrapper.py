@@ -27,11 +27,11 @@ def resolve_fp32_native(fp32_native=None, environ=None) -> bool:
     return environ.get("G2048_ROLLOUT_FP32_NATIVE", "0").strip().lower() in ("1", "true", "yes", "on")
 
 
-SYMMETRY_MODES = ("none", "canonical")
+SYMMETRY_MODES = ("none", "canonical", "ensemble")  # exclusive: canonical + ensemble would average eight copies of one row
 
 
 def resolve_symmetry(symmetry=None, environ=None) -> str:
-    """An explicit argument wins; else G2048_SYMMETRY; default "none".  -> "none" | "canonical"; anything else raises."""
+    """An explicit argument wins; else G2048_SYMMETRY; default "none".  -> one of SYMMETRY_MODES; anything else raises."""
     if symmetry is None:
         environ = os.environ if environ is None else environ
         symmetry = environ.get("G2048_SYMMETRY", "none").strip().lower() or "none"
@@ -56,6 +56,11 @@ class TorchActionFunction:
     runs unchanged on those, and the four logits are turned back into the env's frame (``g2048_sym_logits``).  The policy is then
     exactly equivariant and the value exactly invariant under the symmetries of the board, for one forward; the env, its key
     stream and the trajectory stay in the env's frame.  Train and evaluate an agent in the same mode.
+    ``symmetry="ensemble"`` is for play and needs no retraining: the forward above runs unchanged on all eight views of every board
+    (``g2048_sym_views``, 8 B rows) and ``g2048_sym_fold`` takes the mean over the views, the logits at the action that does in
+    the view what ``a`` does in the env's frame, in an order that depends on the eight addends as a multiset only.  Any agent
+    whose forward treats a row independently of its slot thereby becomes exactly equivariant in policy and exactly invariant in
+    value, at eight times the forward rows.  ``PPOTrainer`` refuses the mode.
     Side effect as in the reference: ``agent`` is moved to ``device`` and put in eval mode.
     """
 
@@ -108,6 +113,8 @@ class TorchActionFunction:
             if logits.shape[0]:
                 nv.sym_logits(logits, frame)  # in place: nothing keeps the forward's output in the canonical frame
             return logits, values
+        if self.symmetry == "ensemble":
+            return self._ensemble(boards, want_logits=True)
         return self._policy(boards)
 
     policy_fn.needs_masks = False  # (RolloutEngine.rollout_policy: no per-lock-step gather of the masks for this policy)
@@ -121,6 +128,27 @@ class TorchActionFunction:
         if boards.shape[0]:
             nv.sym_canon(boards, canon, frame=frame)
         return canon, frame
+
+    def _ensemble(self, boards: torch.Tensor, want_logits: bool = True):
+        """boards u8 [n, 16] -> (logits f32 [n, 4] in the env's frame or None, values f32 [n]): ``self._policy`` on the 8 n view
+        rows, folded.  The fold reads the forward's outputs where they lie (a replayed graph's
+        static outputs included) and writes new tensors."""
+        boards = boards.contiguous()
+        n, dev = boards.shape[0], boards.device
+        out_logits = torch.empty((n, 4), dtype=torch.float32, device=dev) if want_logits else None
+        out_values = torch.empty(n, dtype=torch.float32, device=dev)
+        if n == 0:
+            return out_logits, out_values
+        views = torch.empty((8 * n, 16), dtype=torch.uint8, device=dev)
+        nv.sym_views(boards, views)
+        logits, values = self._policy(views)
+        values = values.to(torch.float32).reshape(-1).contiguous()
+        if want_logits:
+            logits = logits.to(torch.float32).contiguous()
+            if logits.data_ptr() % 16:  # (a view into a larger tensor: the kernel loads 16-byte rows)
+                logits = logits.clone()
+        nv.sym_fold(logits if want_logits else None, values, out_logits, out_values)
+        return out_logits, out_values
 
     def _policy(self, boards: torch.Tensor):
         """The forward as it is without a symmetry mode: fused kernel, replayed graph or module, whichever applies."""
@@ -185,7 +213,7 @@ class TorchActionFunction:
         batched = obs_t.ndim > 3
         obs_t = obs_t.reshape(-1, BOARD_FLAT_DIM, OBS_DIM).float()
         dev = C.device()
-        if self.symmetry == "canonical":  # the one-hot observation is decoded to packed boards and goes down policy_fn
+        if self.symmetry != "none":  # the one-hot observation is decoded to packed boards and goes down policy_fn
             logits, values = self.policy_fn(obs_t.argmax(dim=-1).to(torch.uint8).to(dev), None)
         else:
             agent_dev = next(self.agent.parameters()).device

@@ -48,8 +48,9 @@ def evaluate_agent(agent, device, num_episodes: int = 1000, seed: int = 42, rng_
     seeds, same env and key stream) played by one-ply expectimax over the agent's critic with discount ``gamma``
     (``LookaheadActionFunction``) instead of the actor's argmax; ``lookahead=0`` is the reference's evaluation.  ``expectimax=2``: the same
     protocol played by two-ply expectimax (``ExpectimaxActionFunction``); it excludes ``lookahead``, whose only depth stays 1, and takes
-    no other value than 0 and 2 (one ply is spelled ``lookahead=1``).  ``symmetry``: "none" / "canonical" / None (ask
-    G2048_SYMMETRY), handed to whichever action function is built; evaluate an agent in the mode it was trained in."""
+    no other value than 0 and 2 (one ply is spelled ``lookahead=1``).  ``symmetry``: "none" / "canonical" / "ensemble" / None (ask
+    G2048_SYMMETRY), handed to whichever action function is built; evaluate an agent in the mode it was trained in, or any agent
+    trained without the canonical frame under "ensemble" (the mean over the eight views of every board, no retraining)."""
     from ..ppo.torch_action_wrapper import TorchActionFunction, resolve_symmetry
 
     symmetry = resolve_symmetry(symmetry)

@@ -320,6 +320,29 @@ int g2048_sym_canon(const uint8_t *boards, const uint8_t *actions, const uint8_t
  * G2048_EINVAL: a null pointer, B outside 1 .. 2^30, logits or out not 16-byte aligned. */
 int g2048_sym_logits(const float *logits, const uint8_t *frame, int64_t B, float *out, void *stream);
 
+/* Eight-view ensemble: instead of one forward in a chosen frame, one forward on all eight views and the mean over them,
+ *   L(s)[a] = 1/8 sum_g net_logits(view_g(s))[sigma_g(a)],   V(s) = 1/8 sum_g net_value(view_g(s)).
+ * The views of view_h(s) are the views of s in another order (view_g(view_h(s)) = view_c(s), sigma_g(sigma_h(a)) = sigma_c(a),
+ * c a permutation of g for every h), so the eight addends of L(view_h(s))[sigma_h(a)] are those of L(s)[a] as a multiset.  The
+ * mean is therefore taken in an order that depends on the multiset only: the addends are sorted by the total order of their
+ * bit patterns (-NaN < -inf < .. < -0 < +0 < .. < +inf < +NaN), added in ascending order, each f32 add rounded on its own,
+ * and the sum is multiplied by 0.125f.  With a network whose output for a row depends on that row alone, any agent becomes
+ * exactly equivariant in policy and exactly invariant in value, without retraining.  The result is NaN whenever an addend is
+ * NaN or both infinities occur (payload unspecified). */
+
+/* views u8[B][8][16]: views[b][g] = view_g(boards[b]).  One lane per output row r = 8 b + g, one 16-byte load and one 16-byte
+ * store each; rows at or past 8 B are not touched.  boards is read only and may not overlap views.
+ * G2048_EINVAL: a null pointer, B outside 1 .. 2^27, boards or views not 16-byte aligned. */
+int g2048_sym_views(const uint8_t *boards, int64_t B, uint8_t *views, void *stream);
+
+/* logits f32[8 B][4], values f32[8 B]: a forward's outputs on g2048_sym_views' rows.  out_logits f32[B][4]: out_logits[b][a] =
+ * the mean above of the eight logits[8 b + g][sigma_g(a)]; out_values f32[B]: the same of values[8 b + g].  The pairs
+ * (logits, out_logits) and (values, out_values) are each optional, null together; an output that is not asked for is not
+ * written, rows at or past B are not touched.  One lane per board: 160 B read, 20 B written.  No output may overlap an input.
+ * G2048_EINVAL: exactly one pointer of a pair, both pairs null, B outside 1 .. 2^27, logits or out_logits not 16-byte aligned,
+ * values or out_values not 4-byte aligned. */
+int g2048_sym_fold(const float *logits, const float *values, int64_t B, float *out_logits, float *out_values, void *stream);
+
 /* ---- policy network (update): attention for 17-token sequences ------------------------------------- */
 
 /* softmax(q k^T * scale) v with attention dropout, head_dim 32, Sk = 17 keys, Sq = 17 queries (or 1: the CLS row

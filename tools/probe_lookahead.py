@@ -12,6 +12,8 @@ and of the parts of the lookahead lock-step: the three new kernels, the prefix s
 ``--plies 2`` times the two-ply lock-step (ExpectimaxActionFunction, one slice of roots) and each of its parts instead: both
 expands, the dedup kernel, both prefix sums with their host reads, both children launches, the value forward, both reduces and
 the backup, with ``rows`` (value-forward rows) and ``rows_full`` (the rows without dedup); ``--no-dedup`` skips the dedup launch.
+``--symmetry ensemble`` (or ``canonical``) puts the timed action functions into that mode (the boards are still those of plain
+greedy play): under "ensemble" every forward runs on eight views of its rows, ``children`` / ``rows`` keep counting boards.
 Every figure is the median of ``--repeats`` timed repeats with the min and max next to it.  Prints one JSON line.
 """
 import argparse
@@ -57,11 +59,11 @@ def mid_game_boards(agent, B, dev, steps=96):
     return traj.boards[steps - 1].contiguous()
 
 
-def probe(agent, B, dev, repeats):
+def probe(agent, B, dev, repeats, symmetry="none"):
     boards = mid_game_boards(agent, B, dev)
-    greedy = TorchActionFunction(agent, use_mask=True, sample_actions=False, device=dev, amp_dtype=torch.bfloat16)
-    look = LookaheadActionFunction(agent, device=dev, amp_dtype=torch.bfloat16)
-    res = {"boards": B, "fused_encoder": look._fused is not None,
+    greedy = TorchActionFunction(agent, use_mask=True, sample_actions=False, device=dev, amp_dtype=torch.bfloat16, symmetry=symmetry)
+    look = LookaheadActionFunction(agent, device=dev, amp_dtype=torch.bfloat16, symmetry=symmetry)
+    res = {"boards": B, "symmetry": symmetry, "fused_encoder": look._fused is not None,
            "greedy": timed(lambda: greedy.policy_fn(boards, None), repeats),
            "lookahead": timed(lambda: look.policy_fn(boards, None), repeats)}
     N = look.last_children
@@ -86,8 +88,8 @@ def probe(agent, B, dev, repeats):
         return int(c[-1].item())
 
     def forward():
-        for c0 in range(0, N, look.max_children):
-            values[c0:c0 + look.max_children] = look._values(children[c0:c0 + look.max_children])
+        for c0 in range(0, N, look._chunk):
+            values[c0:c0 + look._chunk] = look._values(children[c0:c0 + look._chunk])
 
     parts = {"expand": timed(lambda: nv.lookahead_expand(boards, after, reward, nchild), repeats),
              "scan_and_host_read": timed(scan, repeats),
@@ -104,11 +106,11 @@ def probe(agent, B, dev, repeats):
     return res
 
 
-def probe2(agent, B, dev, repeats, dedup):
+def probe2(agent, B, dev, repeats, dedup, symmetry="none"):
     """The two-ply lock-step and its parts on the tensors of one expansion (a single slice of roots)."""
     boards = mid_game_boards(agent, B, dev)
-    fn = ExpectimaxActionFunction(agent, plies=2, dedup=dedup, device=dev, amp_dtype=torch.bfloat16)
-    res = {"boards": B, "dedup": dedup, "fused_encoder": fn._fused is not None,
+    fn = ExpectimaxActionFunction(agent, plies=2, dedup=dedup, device=dev, amp_dtype=torch.bfloat16, symmetry=symmetry)
+    res = {"boards": B, "symmetry": symmetry, "dedup": dedup, "fused_encoder": fn._fused is not None,
            "lockstep": timed(lambda: fn.policy_fn(boards, None), repeats)}
     res["rows"], res["rows_full"] = fn.last_children, fn.last_children_full
     res["rows_over_rows_full"] = round(fn.last_children / max(fn.last_children_full, 1), 4)
@@ -159,8 +161,8 @@ def probe2(agent, B, dev, repeats, dedup):
         return torch.stack((c[-1], nchild2.sum(dtype=i32))).tolist() if dedup else int(c[-1].item())
 
     def forward():
-        for c0 in range(0, N2, fn.max_children):
-            values[c0:c0 + fn.max_children] = fn._values(children2[c0:c0 + fn.max_children])
+        for c0 in range(0, N2, fn._chunk):
+            values[c0:c0 + fn._chunk] = fn._values(children2[c0:c0 + fn._chunk])
 
     parts = {"expand1": timed(lambda: nv.lookahead_expand(boards, after1, reward1, nchild1), repeats),
              "scan1_and_host_read": timed(scan1, repeats),
@@ -187,6 +189,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--plies", type=int, default=1, choices=[1, 2], help="2: the two-ply lock-step and its parts")
     ap.add_argument("--no-dedup", action="store_true", help="with --plies 2: value every afterstate's children")
+    ap.add_argument("--symmetry", default="none", choices=["none", "canonical", "ensemble"], help="mode of the timed action functions")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -201,7 +204,7 @@ def main():
     res = {"agent": os.path.basename(a.agent) if a.agent else "fresh weights", "precision": "bfloat16", "repeats": a.repeats,
            "timer": "HIP events around one policy_fn call, 3 warm-up calls, median [min, max]",
            "plies": a.plies,
-           "runs": [probe(agent, B, dev, a.repeats) if a.plies == 1 else probe2(agent, B, dev, a.repeats, not a.no_dedup)
+           "runs": [probe(agent, B, dev, a.repeats, a.symmetry) if a.plies == 1 else probe2(agent, B, dev, a.repeats, not a.no_dedup, a.symmetry)
                     for B in a.boards]}
     print(json.dumps(res))
     if a.out:

@@ -1,7 +1,12 @@
 """Cost of the canonical frame: the two kernels (g2048_sym_canon / g2048_sym_logits) at 65 536 and 2^22 boards (HIP events around
 ``launches`` back-to-back launches, best of 3), and the collect phase of 65 536 boards with and without the mode (same weights,
 same seed, wall time of whole collect_rollouts calls).  Prints one JSON line.
-usage: python tools/probe_symmetry.py [boards for the collect, default 65536] [--no-collect]"""
+usage: python tools/probe_symmetry.py [boards for the collect, default 65536] [--no-collect]
+
+``--ensemble [--agent state_dict.pt] [--out result.json]`` measures the eight-view ensemble instead, by the protocol of
+tools/probe_lookahead.py (HIP events around one call, 3 warm-up calls, median of 7 with min and max): g2048_sym_views and
+g2048_sym_fold at 100, 65 536 and 2^20 boards next to g2048_sym_canon, and the greedy and one-ply lock-steps at 100 and 4 096
+boards with symmetry "none" and "ensemble" on the same weights and boards."""
 import json
 import os
 import sys
@@ -36,6 +41,56 @@ def time_us(fn, launches=20):
         best = us if best is None else min(best, us)
     return round(best, 2)
 
+
+
+
+def ensemble_probe():
+    import probe_lookahead as pl
+    from src.ppo import LookaheadActionFunction, PPOAgent as Agent, TorchActionFunction
+
+    arg = lambda name: sys.argv[sys.argv.index(name) + 1] if name in sys.argv else None
+    torch.manual_seed(0)
+    agent = Agent(**pl.MODEL)
+    if arg("--agent"):
+        agent.load_state_dict(torch.load(arg("--agent"), map_location="cpu"))
+    agent = agent.to(dev).eval()
+    res = {"agent": os.path.basename(arg("--agent")) if arg("--agent") else "fresh weights", "precision": "bfloat16",
+           "timer": "HIP events around one call, 3 warm-up calls, median [min, max] of 7", "kernels": {}, "lockstep": {}}
+    for B in (100, 65536, 1 << 20):
+        boards = torch.randint(0, 12, (B, 16), dtype=torch.uint8, device=dev)
+        canon, frame = torch.empty_like(boards), torch.empty(B, dtype=torch.uint8, device=dev)
+        views = torch.empty((B, 8, 16), dtype=torch.uint8, device=dev)
+        logits, values = torch.randn((8 * B, 4), device=dev), torch.randn(8 * B, device=dev)
+        ol, ov = torch.empty((B, 4), device=dev), torch.empty(B, device=dev)
+        k = {"sym_canon_boards_frame": pl.timed(lambda: nv.sym_canon(boards, canon, frame=frame), 7),      # 33 B per board
+             "sym_views": pl.timed(lambda: nv.sym_views(boards, views), 7),                                # 16 r + 128 w
+             "sym_fold": pl.timed(lambda: nv.sym_fold(logits, values, ol, ov), 7),                          # 160 r + 20 w
+             "sym_fold_values_only": pl.timed(lambda: nv.sym_fold(None, values, None, ov), 7)}              # 32 r + 4 w
+        for name, nbytes in (("sym_canon_boards_frame", 33), ("sym_views", 144), ("sym_fold", 180), ("sym_fold_values_only", 36)):
+            k[name]["GBps"] = round(B * nbytes / k[name]["median_ms"] / 1e6, 1)
+        res["kernels"][str(B)] = k
+    for B in (100, 4096):
+        boards = pl.mid_game_boards(agent, B, dev)
+        row = {}
+        for mode in ("none", "ensemble"):
+            greedy = TorchActionFunction(agent, use_mask=True, sample_actions=False, device=dev, amp_dtype=torch.bfloat16, symmetry=mode)
+            look = LookaheadActionFunction(agent, device=dev, amp_dtype=torch.bfloat16, symmetry=mode)
+            row[mode] = {"greedy": pl.timed(lambda: greedy.policy_fn(boards, None), 7), "greedy_forward_rows": B * (8 if mode == "ensemble" else 1),
+                         "one_ply": pl.timed(lambda: look.policy_fn(boards, None), 7)}
+            row[mode]["one_ply_forward_rows"] = look.last_children * (8 if mode == "ensemble" else 1)
+        for player in ("greedy", "one_ply"):
+            row[player + "_ensemble_over_none"] = round(row["ensemble"][player]["median_ms"] / row["none"][player]["median_ms"], 2)
+        res["lockstep"][str(B)] = row
+    print(json.dumps(res))
+    if arg("--out"):
+        os.makedirs(os.path.dirname(os.path.abspath(arg("--out"))) or ".", exist_ok=True)
+        json.dump(res, open(arg("--out"), "w"), indent=1)
+
+
+if "--ensemble" in sys.argv:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    ensemble_probe()
+    sys.exit(0)
 
 out = {"kernels": {}, "collect": {}}
 for B in (65536, 1 << 22):
