@@ -26,7 +26,7 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 from src.ppo import PPOAgent, PPOTrainer, RolloutBuffer, resolve_symmetry  # noqa: E402
-from src.runs import BatchRunner, evaluate_agent  # noqa: E402
+from src.runs import BatchRunner, evaluate_agent, evaluate_monte_carlo  # noqa: E402
 
 TRAINER = dict(gamma=0.99, lambda_gae=0.95, clip_epsilon=0.2, value_loss_coef=0.5, entropy_coef=0.01, max_grad_norm=0.5,
                target_kl=0.25, use_action_mask=True, mixed_precision="bfloat16", max_samples_per_epoch=300000,
@@ -56,6 +56,10 @@ def main():
     ap.add_argument("--eval-ensemble", action="store_true",
                     help="every evaluation point also plays the same seeds with symmetry='ensemble' (the mean over the eight dihedral views): "
                          "greedy, and the search player of --eval-lookahead when given (key 'ensemble'); not with --symmetry canonical")
+    ap.add_argument("--eval-mc", type=int, default=0, metavar="R",
+                    help="every evaluation point also plays the same seeds by Monte-Carlo playouts, R per move, bootstrapped from the "
+                         "critic of the current weights (key 'monte_carlo'); 0: off")
+    ap.add_argument("--eval-mc-depth", type=int, default=8, metavar="D", help="with --eval-mc: steps per playout before the critic values the leaf")
     ap.add_argument("--save-agent", default=None, help="write the final agent's state_dict here (tools/probe_lookahead.py reads it)")
     a = ap.parse_args()
     if a.eval_ensemble and resolve_symmetry(a.symmetry) == "canonical":
@@ -103,6 +107,14 @@ def main():
                 la.update(depth=a.eval_lookahead, gamma=TRAINER["gamma"])
                 ens["lookahead"] = la
             ev["ensemble"] = ens
+        if ev is not None and a.eval_mc:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            mc = evaluate_monte_carlo(dev, a.eval_episodes, agent=agent, playouts=a.eval_mc, depth=a.eval_mc_depth,
+                                      gamma=TRAINER["gamma"], amp_dtype=torch.bfloat16, symmetry=tr.symmetry)
+            torch.cuda.synchronize()
+            mc.update(playouts=a.eval_mc, depth=a.eval_mc_depth, gamma=TRAINER["gamma"], eval_seconds=round(time.perf_counter() - t0, 1))
+            ev["monte_carlo"] = mc
         if world > 1:
             dist.barrier()
         if ev is not None:
@@ -112,6 +124,10 @@ def main():
             if "lookahead" in ev:
                 la = ev["lookahead"]
                 print(f"  lookahead {la['depth']}: mean max tile {la['mean_max_tile']:.1f}  {la['percent']}  ({la['eval_seconds']} s)", flush=True)
+            if "monte_carlo" in ev:
+                mc = ev["monte_carlo"]
+                print(f"  monte carlo R={mc['playouts']} d={mc['depth']}: mean max tile {mc['mean_max_tile']:.1f}  {mc['percent']}  "
+                      f"({mc['eval_seconds']} s)", flush=True)
             if "ensemble" in ev:
                 ens = ev["ensemble"]
                 print(f"  ensemble: mean max tile {ens['mean_max_tile']:.1f}  {ens['percent']}  ({ens['eval_seconds']} s)", flush=True)

@@ -423,6 +423,33 @@ def sym_fold(logits, values, out_logits, out_values):
            "g2048_sym_fold")
 
 
+def mc_playout(step_subs: np.ndarray, t0: int, roots, B: int, R: int, lane0: int, n_total: int, policy: int, gamma: float,
+               lane_boards, lane_masks, lane_done, lane_ret, lane_disc, rng_mode: int, live_count=None):
+    """``len(step_subs)`` playout steps (global steps t0 ..) of the 4 B R lanes of B roots, R playouts per (board, action) pair.
+    step_subs u32 [n_steps, 4] (host): act sub-key, step sub-key.  t0 == 0 seeds the lanes from roots u8 [B,16]; t0 > 0 continues
+    from the lane arrays (roots may be None).  live_count: i32 [1] zeroed by the caller, or None."""
+    subs = np.ascontiguousarray(step_subs, np.uint32).reshape(-1, 4)
+    B, R = int(B), int(R)
+    n = 4 * B * R
+    _check(load().g2048_mc_playout(subs.ctypes.data, subs.shape[0], int(t0), _dev(roots, u8, 16 * B, "roots", optional=t0 > 0), B, R,
+                                   int(lane0), int(n_total), int(policy), float(gamma), _dev(lane_boards, u8, 16 * n, "lane_boards"),
+                                   _dev(lane_masks, u8, n, "lane_masks"), _dev(lane_done, u8, n, "lane_done"),
+                                   _dev(lane_ret, f32, n, "lane_ret"), _dev(lane_disc, f32, n, "lane_disc"), int(rng_mode),
+                                   _dev(live_count, i32, 1, "live_count", optional=True), _stream()),
+           "g2048_mc_playout")
+
+
+def mc_reduce(lane_ret, lane_disc, lane_done, leaf_values, R: int, q):
+    """q f32 [B,4] = the mean over each pair's R lanes of ret (+ disc * leaf_values where the lane is alive and leaf_values f32
+    [4 B R] is given), summed in ascending lane order."""
+    B, R = q.numel() // 4, int(R)
+    n = 4 * B * R
+    _check(load().g2048_mc_reduce(_dev(lane_ret, f32, n, "lane_ret"), _dev(lane_disc, f32, n, "lane_disc"),
+                                  _dev(lane_done, u8, n, "lane_done"), _dev(leaf_values, f32, n, "leaf_values", optional=True), B, R,
+                                  _dev(q, f32, 4 * B, "q"), _stream()),
+           "g2048_mc_reduce")
+
+
 def attn_fwd(q_ptr: int, k_ptr: int, v_ptr: int, o, lse, B: int, H: int, Sq: int, strides, scale: float, p_drop: float,
              seed: int, seed_state: int = 0):
     """q/k/v: raw device addresses inside bf16 tensors the caller keeps alive; strides = (q_sb, q_ss, k_sb, k_ss,

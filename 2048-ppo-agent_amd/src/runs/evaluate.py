@@ -74,3 +74,18 @@ def evaluate_agent(agent, device, num_episodes: int = 1000, seed: int = 42, rng_
         return evaluate_max_tile(fn, num_episodes, seed, rng_mode=rng_mode, device=device)
     finally:
         agent.train(was_training)
+
+
+def evaluate_monte_carlo(device, num_episodes: int = 1000, seed: int = 42, agent=None, rng_mode=None, **mc_kwargs) -> Dict:
+    """The same protocol (same seeds, same env and key stream) played by ``MonteCarloActionFunction(agent, **mc_kwargs)``: for
+    every legal move ``playouts`` playouts of a cheap policy, the move with the best mean return wins.  ``agent=None``: plain
+    playout returns, no network; with an agent its critic values the leaves the playouts were cut off at (``depth``)."""
+    from ..ppo.monte_carlo import MonteCarloActionFunction
+
+    was_training = agent.training if agent is not None else False
+    fn = MonteCarloActionFunction(agent, device=device, rng_mode=rng_mode, **mc_kwargs)
+    try:
+        return evaluate_max_tile(fn, num_episodes, seed, rng_mode=rng_mode, device=device)
+    finally:
+        if agent is not None:
+            agent.train(was_training)

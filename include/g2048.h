@@ -343,6 +343,44 @@ int g2048_sym_views(const uint8_t *boards, int64_t B, uint8_t *views, void *stre
  * values or out_values not 4-byte aligned. */
 int g2048_sym_fold(const float *logits, const float *values, int64_t B, float *out_logits, float *out_values, void *stream);
 
+/* ---- Monte-Carlo playouts (no reference counterpart: the reference's play only ever asks the actor) -----------------------
+ * For every root board s and every action a, R playouts of a cheap policy from the afterstate:
+ *   Q(s, a) = 1/R sum_r [ sum_t gamma^t r_t  + gamma^d V(leaf_r) ]      (the V term only with leaf values, only for a playout
+ *                                                                         that was cut off alive; Q of an illegal a is +0)
+ * A call has B roots and n = 4 B R lanes: lane j = (4 b + a) R + r is playout r of pair (b, a), and its keys are those of index
+ * g = lane0 + j among n_total (keys = split(sub, n_total)[g], as env0 / B_total of the fused engine: a call cut into slices of
+ * whole boards draws the keys of the uncut call).  Lane state: lane_boards u8[n][16], lane_masks u8[n], lane_done u8[n],
+ * lane_ret f32[n] (discounted return so far), lane_disc f32[n] (gamma^steps played).
+ *   seeding, global step 0: board = roots[b], mask = legal mask of the root, done = !(mask >> a & 1), ret = +0, disc = 1
+ *   a step t of a lane with done == 0: action = a at t == 0 (the act sub-key of step 0 is not used), else the playout policy
+ *     (act_randomly with key split(act_sub_t, n_total)[g], or act_drul) on the lane's mask; r = env.step with key
+ *     split(step_sub_t, n_total)[g]; ret = ret + disc * r, then disc = disc * (float)gamma, every f32 operation rounded on its
+ *     own.  A finished lane is frozen. */
+
+/* n_steps steps (1 .. G2048_MAX_FUSED_STEPS) of every lane, boards resident in registers across them, no trajectory written:
+ * 26 B of lane state read and written per lane (t0 == 0: the 16 B root read instead).  step_subs (host) = [n_steps][4]: act
+ * sub-key, step sub-key of global steps t0 .. t0 + n_steps - 1.  t0 == 0 seeds the lanes from roots u8[B][16] and the lane
+ * arrays are output only; t0 > 0 continues from the lane arrays and roots is not read (may be NULL).  Lanes at or past 4 B R are
+ * not touched.  *live_count (device u32, zeroed by the caller; may be NULL) += lanes still running afterwards, one atomic per
+ * workgroup that has any.
+ * G2048_EINVAL: null step_subs or lane array, null roots at t0 == 0, n_steps outside 1 .. G2048_MAX_FUSED_STEPS, t0 < 0,
+ * R outside 1 .. 1024, B < 1, lane0 < 0, n_total outside 1 .. 2^31 - 1, lane0 + 4 B R > n_total, policy not G2048_POLICY_DRUL /
+ * G2048_POLICY_RANDOM, gamma outside (0, 1] (NaN included), unknown rng_mode, roots or lane_boards not 16-byte aligned,
+ * lane_ret, lane_disc or live_count not 4-byte aligned. */
+int g2048_mc_playout(const uint32_t *step_subs /*host*/, int n_steps, int64_t t0, const uint8_t *roots, int64_t B, int R,
+                     int64_t lane0, int64_t n_total, int policy, double gamma, uint8_t *lane_boards, uint8_t *lane_masks,
+                     uint8_t *lane_done, float *lane_ret, float *lane_disc, int rng_mode, uint32_t *live_count, void *stream);
+
+/* q f32[B][4]: q[b][a] = (x_0 + x_1 + .. + x_{R-1}) / (float)R over the R lanes of pair (b, a), added in ascending r starting
+ * from +0, each add and the one division rounded on their own.  x_r = lane_ret[r] when leaf_values is NULL or the lane is done,
+ * else lane_ret[r] + lane_disc[r] * leaf_values[r] (leaf_values f32[4 B R]: the critic on lane_boards; a finished lane's value
+ * is never read into the sum).  One lane per pair walks its R consecutive lanes: no atomics, the bits do not depend on
+ * scheduling.  Rows at or past B are not touched.
+ * G2048_EINVAL: null lane_ret, lane_disc, lane_done or q, R outside 1 .. 1024, B < 1, 4 B R >= 2^31, an f32 array not 4-byte
+ * aligned. */
+int g2048_mc_reduce(const float *lane_ret, const float *lane_disc, const uint8_t *lane_done, const float *leaf_values, int64_t B,
+                    int R, float *q, void *stream);
+
 /* ---- policy network (update): attention for 17-token sequences ------------------------------------- */
 
 /* softmax(q k^T * scale) v with attention dropout, head_dim 32, Sk = 17 keys, Sq = 17 queries (or 1: the CLS row
