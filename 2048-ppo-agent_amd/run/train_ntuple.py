@@ -1,0 +1,80 @@
+#!/usr/bin/env python3
+"""Train the n-tuple afterstate value network by TD(0) and report its strength on the README protocol.
+
+    python 2048-ppo-agent_amd/run/train_ntuple.py --envs 4096 --minutes 10 --evals 3 --out result.json
+
+Training = ``NTupleTrainer`` on ``--envs`` always-live boards, greedy in the network being learned, in chunks of lock-steps; after
+every chunk one byte per env is read back (the largest tile on a training board).  "First 2048" is the training wall-clock and
+the lock-step count at the end of the first chunk after which a training board holds a 2048 tile.  Evaluation = the histogram
+protocol of ``evaluate_max_tile`` (``--eval-episodes`` episodes, seed 42, batches of 100, largest tile of the final board), at
+``--evals`` points spread evenly over the budget, the last one at its end; evaluation time is excluded from the training clock.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+
+import torch  # noqa: E402
+
+from src.ppo import NTupleNetwork, NTupleTrainer  # noqa: E402
+from src.runs import evaluate_ntuple  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096, help="parallel boards")
+    ap.add_argument("--minutes", type=float, default=10.0, help="training budget (wall-clock, evaluation excluded)")
+    ap.add_argument("--alpha", type=float, default=0.1, help="learning rate of the whole network (split over its 8 m lookups)")
+    ap.add_argument("--evals", type=int, default=3, help="evaluation points, evenly spread, the last at the end of the budget")
+    ap.add_argument("--eval-at", type=float, nargs="*", default=None, help="evaluation points in minutes instead of --evals")
+    ap.add_argument("--eval-episodes", type=int, default=1000)
+    ap.add_argument("--chunk", type=int, default=50, help="lock-steps between two looks at the clock")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the training environments")
+    ap.add_argument("--out", default=None, help="write the JSON result here")
+    ap.add_argument("--save", default=None, help="save the trained network here")
+    args = ap.parse_args()
+
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    net = NTupleNetwork(device=dev)
+    trainer = NTupleTrainer(net, args.envs, alpha=args.alpha, seed=args.seed, device=dev)
+    budget = args.minutes * 60.0
+    points = sorted(60.0 * m for m in args.eval_at) if args.eval_at else [budget * (k + 1) / args.evals for k in range(max(args.evals, 1))]
+    result = dict(envs=args.envs, alpha=args.alpha, seed=args.seed, tuples=[list(t) for t in net.tuples], frac_bits=net.frac_bits,
+                  minutes=args.minutes, first_2048=None, evaluations=[])
+    trained = 0.0
+    episodes = 0
+    while points:
+        t0 = time.perf_counter()
+        out = trainer.train(args.chunk)
+        top = int(trainer.boards.max().item())  # the one host read of a chunk (it also ends the chunk's clock)
+        trained += time.perf_counter() - t0
+        episodes += int(out["episodes"].item())
+        if result["first_2048"] is None and top >= 11:
+            result["first_2048"] = dict(seconds=round(trained, 2), lock_steps=trainer.lock_steps)
+            print(f"first 2048 tile on a training board after {trained:.1f} s, {trainer.lock_steps} lock-steps", flush=True)
+        if trained >= points[0]:
+            points.pop(0)
+            ev = evaluate_ntuple(net, dev, num_episodes=args.eval_episodes, seed=42)
+            ev.update(train_seconds=round(trained, 2), lock_steps=trainer.lock_steps, episodes_trained=episodes,
+                      max_abs_weight=int(net.weights.abs().max().item()))
+            result["evaluations"].append(ev)
+            print(f"{trained / 60:.2f} min, {trainer.lock_steps} lock-steps: mean max tile {ev['mean_max_tile']:.1f}, "
+                  f"percent {ev['percent']}", flush=True)
+    result["lock_steps"] = trainer.lock_steps
+    result["lock_steps_per_s"] = round(trainer.lock_steps / trained, 1)
+    result["env_steps_per_s"] = round(trainer.lock_steps * args.envs / trained, 1)
+    if args.save:
+        net.save(args.save)
+    print(json.dumps(result))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -450,6 +450,63 @@ def mc_reduce(lane_ret, lane_disc, lane_done, leaf_values, R: int, q):
            "g2048_mc_reduce")
 
 
+def _tuple_cells(tuple_cells):
+    """tuple_cells u8 [m, L] (host) -> (contiguous array, m, L)."""
+    cells = np.ascontiguousarray(tuple_cells, np.uint8)
+    if cells.ndim != 2:
+        raise NativeError(f"tuple_cells: expected a [m, L] array of cell indices, got shape {cells.shape}")
+    return cells, cells.shape[0], cells.shape[1]
+
+
+def ntuple_values(boards, weights, tuple_cells, frac_bits: int, values):
+    """values f32 [n] = V(boards u8 [n,16]) of the n-tuple network ``weights`` i32 [m, 16^L] over ``tuple_cells`` u8 [m, L] (host)."""
+    cells, m, L = _tuple_cells(tuple_cells)
+    n = values.numel()
+    _check(load().g2048_ntuple_values(_dev(boards, u8, 16 * n, "boards"), n, _dev(weights, i32, m * 16 ** L, "weights"),
+                                      cells.ctypes.data, m, L, int(frac_bits), _dev(values, f32, n, "values"), _stream()),
+           "g2048_ntuple_values")
+
+
+def ntuple_scores(boards, weights, tuple_cells, frac_bits: int, scores, values):
+    """scores f32 [B,4] = reward + V(afterstate) per action (+0 where illegal), values f32 [B] = the max over the legal ones."""
+    cells, m, L = _tuple_cells(tuple_cells)
+    B = values.numel()
+    _check(load().g2048_ntuple_scores(_dev(boards, u8, 16 * B, "boards"), B, _dev(weights, i32, m * 16 ** L, "weights"),
+                                      cells.ctypes.data, m, L, int(frac_bits), _dev(scores, f32, 4 * B, "scores"),
+                                      _dev(values, f32, B, "values"), _stream()),
+           "g2048_ntuple_scores")
+
+
+def ntuple_td_accumulate(prev_after, flag, target, weights, tuple_cells, frac_bits: int, alpha: float, acc, cnt, td_error=None):
+    """The accumulate half of one TD(0) lock-step: acc i64 [m, 16^L] += delta, cnt i32 [m, 16^L] += 1 at the entries of every env
+    with flag != 0.  td_error f32 [B] or None."""
+    cells, m, L = _tuple_cells(tuple_cells)
+    B, E = flag.numel(), m * 16 ** L
+    _check(load().g2048_ntuple_td_accumulate(_dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"),
+                                             _dev(target, f32, B, "target"), B, _dev(weights, i32, E, "weights"), cells.ctypes.data,
+                                             m, L, int(frac_bits), float(alpha), _dev(acc, i64, E, "acc"), _dev(cnt, i32, E, "cnt"),
+                                             _dev(td_error, f32, B, "td_error", optional=True), _stream()),
+           "g2048_ntuple_td_accumulate")
+
+
+def ntuple_td_apply(prev_after, flag, tuple_cells, weights, acc, cnt):
+    """The apply half: weights += the rounded mean acc / cnt at every entry the same boards hit, acc = cnt = 0 there."""
+    cells, m, L = _tuple_cells(tuple_cells)
+    B, E = flag.numel(), m * 16 ** L
+    _check(load().g2048_ntuple_td_apply(_dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"), B, cells.ctypes.data,
+                                        m, L, _dev(weights, i32, E, "weights"), _dev(acc, i64, E, "acc"), _dev(cnt, i32, E, "cnt"),
+                                        _stream()),
+           "g2048_ntuple_td_apply")
+
+
+def ntuple_link(tr_boards_row, tr_meta_row, prev_after, flag):
+    """prev_after u8 [B,16] = the afterstate of the move recorded in one trajectory row, flag u8 [B] = 2 where it ended the episode."""
+    B = flag.numel()
+    _check(load().g2048_ntuple_link(_dev(tr_boards_row, u8, 16 * B, "tr_boards_row"), _dev(tr_meta_row, u8, B, "tr_meta_row"), B,
+                                    _dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"), _stream()),
+           "g2048_ntuple_link")
+
+
 def attn_fwd(q_ptr: int, k_ptr: int, v_ptr: int, o, lse, B: int, H: int, Sq: int, strides, scale: float, p_drop: float,
              seed: int, seed_state: int = 0):
     """q/k/v: raw device addresses inside bf16 tensors the caller keeps alive; strides = (q_sb, q_ss, k_sb, k_ss,

@@ -2,6 +2,7 @@ from .data_loader import create_ppo_dataloader
 from .expectimax import ExpectimaxActionFunction
 from .lookahead import LookaheadActionFunction
 from .monte_carlo import MonteCarloActionFunction
+from .ntuple import DEFAULT_TUPLES, NTupleActionFunction, NTupleNetwork, NTupleTrainer
 from .ppo_agent import MLPAgent, PPOAgent
 from .ppo_trainer import PPOTrainer
 from .rollout_buffer import RolloutBuffer

@@ -1,0 +1,238 @@
+"""N-tuple afterstate value network: table-lookup play and on-device TD(0) learning (no reference counterpart).
+
+    V(s) = 2^-F * sum over the eight views g of s and the tuples t of weights[t][idx(view_g(s), t)]
+
+The 2048 literature's standard learner: no matrix engine, one evaluation is ``8 m`` gathers, one update ``8 m`` integer atomics.
+The player scores every legal move by ``reward + V(afterstate)`` (``g2048_ntuple_scores``) and the engine takes the masked argmax;
+the trainer learns V by temporal differences between consecutive afterstates of always-live boards, batch-synchronously: all envs
+of a lock-step accumulate into integer tables (``g2048_ntuple_td_accumulate``), every entry that was hit moves by the mean of its
+deltas (``g2048_ntuple_td_apply``).  All accumulation is integer arithmetic, so a run is reproducible bit for bit.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from ..actions import _common as C
+from ..env_definitions import BOARD_FLAT_DIM, OBS_DIM
+from ..g2048 import native as nv
+from ..g2048.engine import seed_key
+
+DEFAULT_TUPLES = ((0, 1, 2, 3, 4, 5), (4, 5, 6, 7, 8, 9), (0, 1, 2, 4, 5, 6), (4, 5, 6, 8, 9, 10))
+MAX_TUPLES, MAX_CELLS, MAX_FRAC_BITS = 8, 6, 20
+
+
+def _check_tuples(tuples) -> np.ndarray:
+    try:
+        rows = [tuple(int(c) for c in t) for t in tuples]
+    except TypeError:
+        raise ValueError(f"tuples must be a sequence of sequences of cell indices, got {tuples!r}") from None
+    if not 1 <= len(rows) <= MAX_TUPLES:
+        raise ValueError(f"the number of tuples must be in 1 .. {MAX_TUPLES}, got {len(rows)}")
+    L = len(rows[0])
+    if not 1 <= L <= MAX_CELLS:
+        raise ValueError(f"a tuple has 1 .. {MAX_CELLS} cells, got {L}")
+    for t in rows:
+        if len(t) != L:
+            raise ValueError(f"all tuples must have the same number of cells, got {rows!r}")
+        if any(not 0 <= c <= 15 for c in t):
+            raise ValueError(f"cell indices are 0 .. 15 (row-major), got {t!r}")
+        if len(set(t)) != L:
+            raise ValueError(f"a tuple's cells must be distinct, got {t!r}")
+    return np.ascontiguousarray(np.array(rows, np.uint8).reshape(len(rows), L))
+
+
+def _device(device) -> torch.device:
+    return C.device() if device is None else torch.device(device)
+
+
+def _mode(rng_mode) -> int:
+    if rng_mode is None:
+        return C.default_rng_mode()
+    if isinstance(rng_mode, str):  # the spellings BatchRunner takes
+        return nv.RNG_LEGACY if rng_mode.lower() in ("legacy", "0") else nv.RNG_PARTITIONABLE
+    return int(rng_mode)
+
+
+class NTupleNetwork:
+    """``weights`` i32 [m, 16^L] (zeros) over ``tuples``: m tuples (1 .. 8) of L distinct cells each (1 .. 6), fixed point with
+    ``frac_bits`` fractional bits (0 .. 20; the default 12 resolves 2.4e-4 and holds +-524 288 per entry).  The default network,
+    four 6-tuples, is 256 MB.  Bad settings raise ``ValueError`` before any device is touched."""
+
+    def __init__(self, tuples=DEFAULT_TUPLES, frac_bits: int = 12, device=None):
+        self.cells = _check_tuples(tuples)
+        if not 0 <= int(frac_bits) <= MAX_FRAC_BITS:
+            raise ValueError(f"frac_bits must be in 0 .. {MAX_FRAC_BITS}, got {frac_bits!r}")
+        self.frac_bits = int(frac_bits)
+        self.tuples = tuple(tuple(int(c) for c in t) for t in self.cells)
+        self.m, self.L = self.cells.shape
+        self.device = _device(device)
+        self.weights = torch.zeros((self.m, 16 ** self.L), dtype=torch.int32, device=self.device)
+
+    def values(self, boards: torch.Tensor) -> torch.Tensor:
+        """boards u8 [n, 16] -> V f32 [n]."""
+        boards = boards.contiguous()
+        out = torch.empty(boards.shape[0], dtype=torch.float32, device=boards.device)
+        if out.numel():
+            nv.ntuple_values(boards, self.weights, self.cells, self.frac_bits, out)
+        return out
+
+    def scores(self, boards: torch.Tensor):
+        """boards u8 [B, 16] -> (q f32 [B, 4], v f32 [B]): q[a] = reward + V(afterstate) of a legal move and +0 of an illegal one,
+        v = the max over the legal moves (0 if there is none)."""
+        boards = boards.contiguous()
+        B = boards.shape[0]
+        q = torch.empty((B, 4), dtype=torch.float32, device=boards.device)
+        v = torch.empty(B, dtype=torch.float32, device=boards.device)
+        if B:
+            nv.ntuple_scores(boards, self.weights, self.cells, self.frac_bits, q, v)
+        return q, v
+
+    def save(self, path: str) -> None:
+        torch.save({"weights": self.weights.cpu(), "tuples": self.tuples, "frac_bits": self.frac_bits}, path)
+
+    @classmethod
+    def load(cls, path: str, device=None) -> "NTupleNetwork":
+        d = torch.load(path, map_location="cpu")
+        net = cls(d["tuples"], d["frac_bits"], device=device)
+        if tuple(d["weights"].shape) != tuple(net.weights.shape) or d["weights"].dtype != torch.int32:
+            raise ValueError(f"{path}: weights of shape {tuple(d['weights'].shape)} do not fit tuples {net.tuples}")
+        net.weights.copy_(d["weights"])
+        return net
+
+
+class NTupleActionFunction:
+    """``act_fn`` plug-in for ``BatchRunner`` whose "logits" are the n-tuple network's afterstate scores.
+
+    ``policy_fn(boards, masks)`` returns ``(q f32 [B, 4], v f32 [B])`` of ``NTupleNetwork.scores``.  ``use_mask=True,
+    sample_actions=False`` are forced, so the engine (``g2048_policy_step``) takes the masked argmax of ``q``; the env, its key
+    stream and the trajectory format are untouched.  The recorded ``log_prob`` is the log-softmax of scores at the chosen action:
+    NOT a policy probability (``q`` is in score units), so such trajectories are for evaluation only, not for a PPO update.
+    """
+
+    use_mask = True
+    sample_actions = False
+    compact = True
+
+    def __init__(self, network: NTupleNetwork, device=None, rng_mode=None):
+        if not isinstance(network, NTupleNetwork):
+            raise ValueError(f"network must be an NTupleNetwork, got {type(network).__name__}")
+        self.network = network
+        self.device = device
+        self.rng_mode = rng_mode
+
+    @torch.no_grad()
+    def policy_fn(self, boards: torch.Tensor, masks: torch.Tensor = None):
+        """boards u8 [B, 16], masks unused (legality is ``afterstate != board``) -> (q f32 [B, 4], v f32 [B])."""
+        return self.network.scores(boards)
+
+    policy_fn.needs_masks = False
+
+    @torch.no_grad()
+    def __call__(self, rng_key, obs, mask):
+        """Un-batched plug-in protocol ``(rng_key[2], obs[4,4,31], mask[4]) -> (action, log_prob, value)``; leading batch
+        dimensions are accepted.  The one-hot observation is decoded to a packed board and goes down ``policy_fn``."""
+        obs_t = torch.as_tensor(np.asarray(obs.cpu() if isinstance(obs, torch.Tensor) else obs))
+        batched = obs_t.ndim > 3
+        dev = C.device()
+        boards = obs_t.reshape(-1, BOARD_FLAT_DIM, OBS_DIM).to(torch.float32).argmax(dim=-1).to(torch.uint8).to(dev)
+        q, values = self.policy_fn(boards, None)
+        bits = C.mask_to_bits(mask)
+        keys = C.keys_tensor(rng_key)
+        n = bits.numel()
+        actions = torch.empty(n, dtype=torch.int32, device=dev)
+        logp = torch.empty(n, dtype=torch.float32, device=dev)
+        nv.act_logits(keys, q.contiguous(), bits, True, False, actions, logp, _mode(self.rng_mode))
+        a, lp, v = actions.cpu().numpy(), logp.cpu().numpy(), values.cpu().numpy()
+        if batched:
+            return a, lp, v
+        return np.int32(a[0]), np.float32(lp[0]), np.float32(v[0])
+
+
+class NTupleTrainer:
+    """TD(0) on afterstates over ``num_envs`` always-live boards, greedy in the network being learned.
+
+    One lock-step is five launches on the ambient stream: scores of the current boards (their max is the TD target of the
+    previous afterstate) -> ``td_accumulate`` -> ``td_apply`` -> the engine's auto-reset step on the masked argmax of the scores
+    (``use_mask=1, sample=0``, a one-row trajectory) -> ``link``, which replays the recorded move to get the new afterstate and
+    reads the done bit.  The key chain advances as in ``RolloutEngine.rollout_policy_fixed``: the init split at the first call,
+    then two sub-keys per lock-step.  Nothing is read back inside the loop; env state and learner state persist across calls.
+    """
+
+    def __init__(self, network: NTupleNetwork, num_envs: int, alpha: float = 0.1, seed: int = 0, rng_mode=None, device=None):
+        if not isinstance(network, NTupleNetwork):
+            raise ValueError(f"network must be an NTupleNetwork, got {type(network).__name__}")
+        if int(num_envs) < 1:
+            raise ValueError(f"num_envs must be positive, got {num_envs!r}")
+        if not (float(alpha) > 0.0 and np.isfinite(float(alpha))):
+            raise ValueError(f"alpha must be a finite positive number, got {alpha!r}")
+        self.network = network
+        self.num_envs = B = int(num_envs)
+        self.alpha = float(alpha)
+        self.rng_mode = _mode(rng_mode)
+        self.device = dev = network.device if device is None else torch.device(device)
+        if dev != network.weights.device:
+            raise ValueError(f"the trainer's device {dev} is not the network's {network.weights.device}")
+        self.key = seed_key(int(seed))
+        u8, f32 = torch.uint8, torch.float32
+        self.acc = torch.zeros(network.weights.shape, dtype=torch.int64, device=dev)
+        self.cnt = torch.zeros(network.weights.shape, dtype=torch.int32, device=dev)
+        self.prev_after = torch.zeros((B, 16), dtype=u8, device=dev)
+        self.flag = torch.zeros(B, dtype=u8, device=dev)
+        self.boards = torch.empty((B, 16), dtype=u8, device=dev)
+        self.masks = torch.empty(B, dtype=u8, device=dev)
+        self.ep_len = torch.empty(B, dtype=torch.int32, device=dev)
+        self._done = torch.empty(B, dtype=u8, device=dev)
+        self.scores = torch.empty((B, 4), dtype=f32, device=dev)
+        self.targets = torch.empty(B, dtype=f32, device=dev)
+        self.td_error = torch.empty(B, dtype=f32, device=dev)
+        self._tr = dict(boards=torch.empty((1, B, 16), dtype=u8, device=dev), meta=torch.empty((1, B), dtype=u8, device=dev),
+                        rewards=torch.empty((1, B), dtype=f32, device=dev), logp=torch.empty((1, B), dtype=f32, device=dev),
+                        values=torch.empty((1, B), dtype=f32, device=dev))
+        self._started = False
+        self.lock_steps = 0
+
+    @torch.no_grad()
+    def train(self, lock_steps: int, record: bool = False):
+        """``lock_steps`` lock-steps -> {"episodes": i64 [], "td_sq_sum": f64 []} (device tensors: episodes finished, sum of
+        td_error^2).  ``record=True`` adds per-step copies "boards" u8 [T, B, 16] (before the step), "meta" u8 [T, B], "scores"
+        f32 [T, B, 4] and "targets" f32 [T, B]: for replaying a run in a test, not for training."""
+        T, B, net, tr = int(lock_steps), self.num_envs, self.network, self._tr
+        if T < 1:
+            raise ValueError(f"lock_steps must be positive, got {lock_steps!r}")
+        if not self._started:
+            self.key, sub = nv.chain_keys(self.key, 1, self.rng_mode)
+            nv.reset_fused(sub[0], self.boards, self.masks, self._done, self.ep_len, B, 0, self.rng_mode)
+            self._started = True
+        self.key, subs = nv.chain_keys(self.key, 2 * T, self.rng_mode)
+        episodes = torch.zeros((), dtype=torch.int64, device=self.device)
+        td_sq = torch.zeros((), dtype=torch.float64, device=self.device)
+        rec = None
+        if record:
+            rec = dict(boards=torch.empty((T, B, 16), dtype=torch.uint8, device=self.device),
+                       meta=torch.empty((T, B), dtype=torch.uint8, device=self.device),
+                       scores=torch.empty((T, B, 4), dtype=torch.float32, device=self.device),
+                       targets=torch.empty((T, B), dtype=torch.float32, device=self.device))
+        for t in range(T):
+            nv.ntuple_scores(self.boards, net.weights, net.cells, net.frac_bits, self.scores, self.targets)
+            nv.ntuple_td_accumulate(self.prev_after, self.flag, self.targets, net.weights, net.cells, net.frac_bits, self.alpha,
+                                    self.acc, self.cnt, self.td_error)
+            nv.ntuple_td_apply(self.prev_after, self.flag, net.cells, net.weights, self.acc, self.cnt)
+            nv.policy_step_autoreset(subs[2 * t], subs[2 * t + 1], self.scores, self.targets, True, False, 0, self.boards, self.masks,
+                                     self.ep_len, tr["boards"], tr["meta"], tr["rewards"], tr["logp"], tr["values"], B, 0,
+                                     self.rng_mode)
+            nv.ntuple_link(tr["boards"][0], tr["meta"][0], self.prev_after, self.flag)
+            episodes += (self.flag == 2).sum()
+            td_sq += self.td_error.double().square().sum()
+            if rec is not None:
+                rec["boards"][t].copy_(tr["boards"][0])
+                rec["meta"][t].copy_(tr["meta"][0])
+                rec["scores"][t].copy_(self.scores)
+                rec["targets"][t].copy_(self.targets)
+        self.lock_steps += T
+        out = {"episodes": episodes, "td_sq_sum": td_sq}
+        if rec is not None:
+            out.update(rec)
+        return out

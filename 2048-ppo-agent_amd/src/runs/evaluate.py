@@ -89,3 +89,12 @@ def evaluate_monte_carlo(device, num_episodes: int = 1000, seed: int = 42, agent
     finally:
         if agent is not None:
             agent.train(was_training)
+
+
+def evaluate_ntuple(network, device, num_episodes: int = 1000, seed: int = 42, rng_mode=None) -> Dict:
+    """The same protocol (same seeds, same env and key stream) played by ``NTupleActionFunction(network)``: the legal move with the
+    best ``reward + V(afterstate)`` under the n-tuple network, no other network or search involved."""
+    from ..ppo.ntuple import NTupleActionFunction
+
+    fn = NTupleActionFunction(network, device=device, rng_mode=rng_mode)
+    return evaluate_max_tile(fn, num_episodes, seed, rng_mode=rng_mode, device=device)

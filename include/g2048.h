@@ -381,6 +381,62 @@ int g2048_mc_playout(const uint32_t *step_subs /*host*/, int n_steps, int64_t t0
 int g2048_mc_reduce(const float *lane_ret, const float *lane_disc, const uint8_t *lane_done, const float *leaf_values, int64_t B,
                     int R, float *q, void *stream);
 
+/* ---- n-tuple network (no reference counterpart: a value function made of table lookups, learned by TD(0) on afterstates) ----
+ * m tuples (1 .. 8) of L distinct cells each (1 .. 6, row-major cell indices 0 .. 15): tuple_cells u8[m][L], a HOST pointer
+ * whose bytes travel in the kernarg.  weights i32[m][16^L], fixed point with frac_bits F (0 .. 20) fractional bits.
+ *   idx(x, t) = sum_j min(x[c_tj], 15) << 4 j             (log2 tiles above 15 are clamped: the index never leaves the table)
+ *   S(board)  = sum over g = 0 .. 7 and t of weights[t][idx(view_g(board), t)], an int64 sum; view_g as in the canonical frame
+ *   V(board)  = (float)S * 2^-F: one int64 -> f32 conversion (round to nearest even), one exact multiply
+ * Batch-synchronous TD(0): every env keeps prev_after u8[16], the afterstate of its last move, and flag u8: 0 no predecessor,
+ * 1 a predecessor whose successor is the env's current board, 2 a predecessor whose step ended the episode.  Per lock-step,
+ * with target = v(current board) for flag 1 and 0 for flag 2:
+ *   e = target - V(prev_after) (one f32 subtraction), d = e * c with c = (float)(alpha * 2^F / (8 m)) (computed in double),
+ *   d clamped to +-2^30, delta = (int32) rint(d) (half to even);
+ *   accumulate: for every env with flag != 0, every view g and tuple t: acc[t][i] += delta, cnt[t][i] += 1 at
+ *     i = idx(view_g(prev_after), t); a board that hits an entry several times counts each time;
+ *   apply: for every entry with cnt > 0: weights = sat_int32(weights + rdiv(acc, cnt)), acc = cnt = 0, with
+ *     rdiv(a, c) = sign(a) * ((2 |a| + c) / (2 c)) in int64 (the mean, rounded half away from zero).
+ * acc i64[m][16^L] and cnt i32[m][16^L] are all-zero between lock-steps.  Every accumulation is an integer one: the result
+ * does not depend on scheduling.  No entry point allocates or synchronises; every argument check precedes any device work. */
+
+/* values f32[n]: values[i] = V(boards[i]).  One lane per board, 8 m gathers each; rows at or past n are not touched.
+ * G2048_EINVAL: a null pointer, n outside 1 .. 2^28, m outside 1 .. 8, L outside 1 .. 6, a cell above 15, a cell twice in one
+ * tuple, frac_bits outside 0 .. 20, boards not 16-byte aligned, weights or values not 4-byte aligned. */
+int g2048_ntuple_values(const uint8_t *boards, int64_t n, const int32_t *weights, const uint8_t *tuple_cells /*host*/, int m, int L,
+                        int frac_bits, float *values, void *stream);
+
+/* scores f32[B][4]: scores[b][a] = (float)r_a + V(after_a) (one rounded add) with after_a, r_a = move(boards[b], a) where
+ * after_a != boards[b], +0 where the move is illegal.  values f32[B]: the max of scores[b] over the legal a, 0 if there is
+ * none.  One lane per (board, action) pair, all 8 m gathers of a lane in flight together, the max by quad cross-lane moves;
+ * rows at or past B are not touched.
+ * G2048_EINVAL: as g2048_ntuple_values (B for n), scores not 4-byte aligned. */
+int g2048_ntuple_scores(const uint8_t *boards, int64_t B, const int32_t *weights, const uint8_t *tuple_cells /*host*/, int m, int L,
+                        int frac_bits, float *scores, float *values, void *stream);
+
+/* The accumulate half of a lock-step (above).  prev_after u8[B][16], flag u8[B], target f32[B] (read where flag == 1 only);
+ * weights are only read.  td_error f32[B] (may be NULL) = e, 0 where flag == 0.  One lane per env: 8 m gathers, then 8 m
+ * 64-bit and 8 m 32-bit atomic adds.
+ * G2048_EINVAL: a null pointer other than td_error, B outside 1 .. 2^28, the network as above, alpha not a finite positive
+ * number, prev_after not 16-byte aligned, acc not 8-byte aligned, target, weights, cnt or td_error not 4-byte aligned. */
+int g2048_ntuple_td_accumulate(const uint8_t *prev_after, const uint8_t *flag, const float *target, int64_t B,
+                               const int32_t *weights, const uint8_t *tuple_cells /*host*/, int m, int L, int frac_bits, double alpha,
+                               int64_t *acc, int32_t *cnt, float *td_error, void *stream);
+
+/* The apply half, in a launch of its own after g2048_ntuple_td_accumulate on the same prev_after and flag: the entries of the
+ * same boards are visited again, cnt is exchanged for 0 and the one lane that finds cnt > 0 updates the entry.  The tables
+ * are never scanned: the cost is that of the 8 m entries per env.
+ * G2048_EINVAL: a null pointer, B outside 1 .. 2^28, the network as above, prev_after not 16-byte aligned, acc not 8-byte
+ * aligned, weights or cnt not 4-byte aligned. */
+int g2048_ntuple_td_apply(const uint8_t *prev_after, const uint8_t *flag, int64_t B, const uint8_t *tuple_cells /*host*/, int m, int L,
+                          int32_t *weights, int64_t *acc, int32_t *cnt, void *stream);
+
+/* After the env step: prev_after[b] = move(tr_boards_row[b], action), flag[b] = done_after ? 2 : 1, action and done_after read
+ * from tr_meta_row[b] = action | mask_before << 2 | done_after << 6, the trajectory row the engine has just written (the
+ * learner follows whatever the policy played).  One lane per env.
+ * G2048_EINVAL: a null pointer, B outside 1 .. 2^28, tr_boards_row or prev_after not 16-byte aligned. */
+int g2048_ntuple_link(const uint8_t *tr_boards_row, const uint8_t *tr_meta_row, int64_t B, uint8_t *prev_after, uint8_t *flag,
+                      void *stream);
+
 /* ---- policy network (update): attention for 17-token sequences ------------------------------------- */
 
 /* softmax(q k^T * scale) v with attention dropout, head_dim 32, Sk = 17 keys, Sq = 17 queries (or 1: the CLS row

@@ -1,0 +1,178 @@
+#!/usr/bin/env python3
+"""N-tuple network on one GPU: time per launch of its five kernels, the training lock-step, the player's lock-step, learning speed.
+
+    python tools/probe_ntuple.py [--out profiles/ntuple_probe.json]
+
+Timing: HIP events around one call, 3 warm-up calls, median of ``--repeats`` with min and max, one process (the style of
+tools/probe_mc.py).
+  (a) every kernel at 4 096 and 65 536 boards of the default network in two board states: "reset" (every board freshly reset, one
+      lock-step played so that each env has a predecessor) and "trained" (``--train-steps`` lock-steps into training at that env
+      count).  td_accumulate is timed on zeroed acc / cnt and td_apply after an untimed accumulate (both restored outside the
+      events); next to the times: gathers and atomics per launch, the number of distinct entries hit and the largest number of
+      same-address atomics of the launch (the max of cnt).
+  (b) the whole training lock-step (``NTupleTrainer.train``, per lock-step) at 1 024, 4 096 and 65 536 envs.
+  (c) the player's lock-step (``NTupleActionFunction.policy_fn``) at 100 and 4 096 boards after ``--board-steps`` lock-steps of
+      random play, next to the greedy-agent and one-ply lock-steps of a fresh-weights PPOAgent on the same boards.
+  (d) learning speed: mean max tile over ``--episodes`` evaluation episodes (seed 42) after ``--learn-steps`` lock-steps at 1 024,
+      4 096 and 65 536 envs, from zero weights, one seed each.
+Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, "..", "2048-ppo-agent_amd"))
+
+import torch  # noqa: E402
+
+from src.g2048 import native as nv  # noqa: E402
+from src.ppo import (LookaheadActionFunction, NTupleActionFunction, NTupleNetwork, NTupleTrainer, PPOAgent,  # noqa: E402
+                     TorchActionFunction)
+from src.runs import BatchRunner, evaluate_ntuple  # noqa: E402
+
+MODEL = dict(observation_dim=31, action_dim=4, hidden_dim=512, d_model=256, nhead=8, num_layers=4, dim_feedforward=1024,
+             dropout=0.1, reduction="cls")
+
+
+def timed(fn, repeats, warmup=3, setup=None):
+    ms = []
+    for i in range(warmup + repeats):
+        if setup is not None:
+            setup()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        if i >= warmup:
+            ms.append(a.elapsed_time(b))
+    return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
+
+
+def kernel_state(trainer, label, repeats):
+    """The five kernels on the trainer's current boards / prev_after / flag."""
+    net, B = trainer.network, trainer.num_envs
+    w, cells, F = net.weights, net.cells, net.frac_bits
+    m = net.m
+    saved = w.clone()
+    values = torch.empty(B, dtype=torch.float32, device=w.device)
+    prev, flag = trainer.prev_after.clone(), trainer.flag.clone()
+    tr = trainer._tr
+
+    def zero():
+        trainer.acc.zero_(), trainer.cnt.zero_()
+
+    def accumulate():
+        nv.ntuple_td_accumulate(trainer.prev_after, trainer.flag, trainer.targets, w, cells, F, trainer.alpha, trainer.acc, trainer.cnt,
+                                trainer.td_error)
+
+    def prepare_apply():
+        zero(), accumulate()
+
+    nv.ntuple_scores(trainer.boards, w, cells, F, trainer.scores, trainer.targets)
+    zero(), accumulate()
+    live = int((trainer.flag != 0).sum().item())
+    res = {"state": label, "boards": B, "envs_with_predecessor": live,
+           "distinct_entries_hit": int((trainer.cnt > 0).sum().item()), "max_same_address_atomics": int(trainer.cnt.max().item()),
+           "per_launch": {"values": f"{8 * m * B} gathers", "scores": f"<= {4 * 8 * m * B} gathers (legal moves only)",
+                          "td_accumulate": f"{8 * m * live} gathers, {8 * m * live} 64-bit + {8 * m * live} 32-bit atomic adds",
+                          "td_apply": f"{8 * m * live} atomic exchanges, one read-modify-write of weights and acc per distinct entry",
+                          "link": f"{B} boards, 17 B in, 17 B out"}}
+    res["values"] = timed(lambda: nv.ntuple_values(trainer.boards, w, cells, F, values), repeats)
+    res["scores"] = timed(lambda: nv.ntuple_scores(trainer.boards, w, cells, F, trainer.scores, trainer.targets), repeats)
+    res["td_accumulate"] = timed(accumulate, repeats, setup=zero)
+    res["td_apply"] = timed(lambda: nv.ntuple_td_apply(trainer.prev_after, trainer.flag, cells, w, trainer.acc, trainer.cnt), repeats,
+                            setup=prepare_apply)
+    res["link"] = timed(lambda: nv.ntuple_link(tr["boards"][0], tr["meta"][0], prev, flag), repeats)
+    w.copy_(saved)  # the timed applies moved the weights
+    zero()
+    return res
+
+
+def kernel_probe(B, dev, repeats, train_steps):
+    net = NTupleNetwork(device=dev)
+    trainer = NTupleTrainer(net, B, device=dev)
+    trainer.train(1)
+    out = [kernel_state(trainer, "reset: one lock-step after a reset of all boards", repeats)]
+    trainer.train(train_steps - 1)
+    out.append(kernel_state(trainer, f"trained: {train_steps} lock-steps into training", repeats))
+    return out
+
+
+def train_probe(B, dev, repeats, chunk=50):
+    trainer = NTupleTrainer(NTupleNetwork(device=dev), B, device=dev)
+    t = timed(lambda: trainer.train(chunk), repeats)
+    return {"envs": B, "lock_steps_per_call": chunk, **{k.replace("_ms", "_ms_per_lock_step"): round(v / chunk, 4) for k, v in t.items()}}
+
+
+def play_boards(B, dev, board_steps):
+    traj = BatchRunner(init_seed=7, device=dev)._engine.rollout_fused(B, nv.POLICY_RANDOM, fill_frozen=True)
+    t = min(board_steps, traj.T - 1)
+    return traj.boards[t].contiguous().clone()
+
+
+def lockstep_probe(net, agent, B, dev, repeats, board_steps):
+    boards = play_boards(B, dev, board_steps)
+    player = NTupleActionFunction(net, device=dev)
+    greedy = TorchActionFunction(agent, use_mask=True, sample_actions=False, device=dev, amp_dtype=torch.bfloat16)
+    look = LookaheadActionFunction(agent, device=dev, amp_dtype=torch.bfloat16)
+    return {"boards": B, "board_steps": board_steps, "ntuple": timed(lambda: player.policy_fn(boards, None), repeats),
+            "greedy_agent": timed(lambda: greedy.policy_fn(boards, None), repeats),
+            "one_ply_lookahead": timed(lambda: look.policy_fn(boards, None), repeats)}
+
+
+def learning_probe(B, dev, steps, episodes):
+    net = NTupleNetwork(device=dev)
+    out = NTupleTrainer(net, B, device=dev).train(steps)
+    ev = evaluate_ntuple(net, dev, num_episodes=episodes, seed=42)
+    return {"envs": B, "lock_steps": steps, "training_episodes": int(out["episodes"].item()), "eval_episodes": episodes,
+            "mean_max_tile": ev["mean_max_tile"], "percent": ev["percent"], "max_abs_weight": int(net.weights.abs().max().item())}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--boards", type=int, nargs="+", default=[4096, 65536])
+    ap.add_argument("--envs", type=int, nargs="+", default=[1024, 4096, 65536])
+    ap.add_argument("--player-boards", type=int, nargs="+", default=[100, 4096])
+    ap.add_argument("--train-steps", type=int, default=2000)
+    ap.add_argument("--learn-steps", type=int, default=800)
+    ap.add_argument("--episodes", type=int, default=200)
+    ap.add_argument("--board-steps", type=int, default=48)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("probe_ntuple.py measures on the GPU; none is visible")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    torch.manual_seed(0)
+    agent = PPOAgent(**MODEL).to(dev).eval()
+    res = {"command": "python tools/probe_ntuple.py " + " ".join(sys.argv[1:]), "device": torch.cuda.get_device_name(dev),
+           "network": "4 x 6-tuples (default), frac_bits 12, alpha 0.1", "repeats": a.repeats,
+           "timer": "HIP events around one call, 3 warm-up calls, median [min, max]", "kernels": [], "training_lock_step": [],
+           "player_lock_step": [], "learning": []}
+    for B in a.boards:
+        res["kernels"] += kernel_probe(B, dev, a.repeats, a.train_steps)
+        print(json.dumps(res["kernels"][-2:]), flush=True)
+    for B in a.envs:
+        res["training_lock_step"].append(train_probe(B, dev, a.repeats))
+        print(json.dumps(res["training_lock_step"][-1]), flush=True)
+    net = NTupleNetwork(device=dev)
+    for B in a.player_boards:
+        res["player_lock_step"].append(lockstep_probe(net, agent, B, dev, a.repeats, a.board_steps))
+        print(json.dumps(res["player_lock_step"][-1]), flush=True)
+    del net
+    for B in a.envs:
+        res["learning"].append(learning_probe(B, dev, a.learn_steps, a.episodes))
+        print(json.dumps(res["learning"][-1]), flush=True)
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)) or ".", exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
