@@ -747,7 +747,7 @@ extern "C" int g2048_cls_tail_fwd(const void *o, const float *x_cls, int64_t x_r
         if (!p || !aligned16(p)) return G2048_EINVAL;
     if (!values || !S->mean || !S->rstd || ((uintptr_t)values & 3)) return G2048_EINVAL;
     const int64_t blocks = (M + TB - 1) / TB;
-    if (S->ld < blocks * TB || (S->ld & 7)) return G2048_EINVAL;
+    if (S->ld < blocks * TB || (S->ld & 15)) return G2048_EINVAL;
     if (const int rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_tail_fwd), (int)sizeof(TailLds))) return rc;
     hipLaunchKernelGGL(k_tail_fwd, dim3((unsigned)blocks, 2), dim3(THREADS), sizeof(TailLds), (hipStream_t)stream, (const __bf16 *)o, x_cls,
                        x_row_stride, *W, *S, logits, values, M, eps, p_drop, seed, seed_state);
@@ -765,7 +765,7 @@ extern "C" int g2048_cls_tail_bwd(const float *dlogits, const float *dvalues, co
         if (!p || !aligned16(p)) return G2048_EINVAL;
     if (!dvalues || !S->mean || !S->rstd || ((uintptr_t)dvalues & 3)) return G2048_EINVAL;
     const int64_t blocks = (M + TB - 1) / TB;
-    if (S->ld < blocks * TB || (S->ld & 7)) return G2048_EINVAL;
+    if (S->ld < blocks * TB || (S->ld & 15)) return G2048_EINVAL;
     if (const int rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_tail_bwd), (int)sizeof(TailLds))) return rc;
     hipLaunchKernelGGL(k_tail_bwd, dim3((unsigned)blocks), dim3(THREADS), sizeof(TailLds), (hipStream_t)stream, dlogits, dvalues, *WT, *S, *G,
                        (__bf16 *)d_o, dx_cls, M, p_drop, seed, seed_state);

@@ -797,7 +797,9 @@ typedef struct {
  * The weights of g2048_tail_weights / g2048_tail_weights_t (except a3, c3: row-major) and every transposed activation buffer
  * below are stored that way; g2048_opt_step maintains packed shadows of parameters (g2048_opt_chunk.shadow_p / shadow_tp). */
 /* What the forward leaves for the backward and for the weight gradients.  ld = number of columns of every transposed
- * buffer, a multiple of 32 and >= 32 * ceil(M / 32); columns M..ld-1 are written as zero.
+ * buffer, >= 32 * ceil(M / 32) and a multiple of 16 (the packed layout has ld / 16 k-steps per row tile; both entry points return
+ * G2048_EINVAL otherwise, as g2048_dweight_t does; the product passes multiples of 32); columns M..32 * ceil(M / 32) - 1 are written
+ * as zero, columns beyond that are not written: allocate the buffers zero-filled.
  * masks: u16 [ceil(M/32)][G2048_TAIL_MASK_TILES][64], one bit per element of an MFMA accumulator tile (private layout). */
 #define G2048_TAIL_MASK_TILES 96
 typedef struct {
@@ -805,7 +807,7 @@ typedef struct {
     void *masks;
     void *oT, *h2T, *uT, *featsT;       /* bf16 [256][ld], [256][ld], [1024][ld], [256][ld]: inputs of out_proj, linear1, linear2, heads */
     void *a1T, *a2T, *c1T, *c2T;        /* bf16 [512][ld] each: hidden activations of the heads */
-    int64_t ld;
+    int64_t ld;                         /* columns of every transposed buffer: a multiple of 16, >= 32 * ceil(M / 32) */
 } g2048_tail_saved;
 /* dY^T of every Linear (bf16, [out][ld]; dlT / dvT have 32 rows of which 4 / 1 are written: allocate them zero-filled) and
  * the LayerNorm gradient partials f32 [ceil(M/32)][2][256] (dgamma | dbeta per workgroup, for g2048_reduce_jobs). */

@@ -1,6 +1,7 @@
 """The fused CLS tail of the update (g2048_cls_tail_fwd / _bwd + g2048_dweight_t, csrc/g2048_tail.hip) against plain PyTorch
 compositions of the same operators (reference: nn.TransformerEncoderLayer(norm_first=True) of src/ppo/transformer_encoder.py:138-148
-after its attention, and the actor / critic heads of src/ppo/ppo_agent.py:62-92)."""
+after its attention, and the actor / critic heads of src/ppo/ppo_agent.py:62-92).
+The exact test of the three kernels (every saved tensor, mask word and gradient per element against float64) is tests/test_gpu_tail_f64.py."""
 import copy
 
 import numpy as np
