@@ -4,7 +4,8 @@
     Q2(s, a) = r(s, a) + gamma * E_spawn V1(s')
 
 Env model, spawn law, child order and per-operation f32 rounding are those of the one-ply kernels (``lookahead.py``), which
-run on both levels: a level-1 child is just a board.  Per lock-step and slice of roots:
+run on both levels: a level-1 child is just a board, so both levels are built from that module's ``expand_level`` (= ``expand`` +
+``scan``; level 2 scans after the dedup), ``spawn_children`` and the parent's ``values``.  Per lock-step and slice of roots:
 
     expand(boards) -> cumsum, host read 1 -> children                           children1 [N1,16], terminal1, offset1
     expand(children1)                                                           after2 [N1,4,16], reward2, nchild2
@@ -27,7 +28,7 @@ from typing import Optional
 import torch
 
 from ..g2048 import native as nv
-from .lookahead import LookaheadActionFunction
+from .lookahead import LookaheadActionFunction, expand, expand_level, scan, spawn_children
 
 MAX_CHILDREN_PER_BOARD = 120  # one tile: 4 legal moves x 15 empty cells x 2 tiles
 MAX_SLICE_CHILDREN = 1 << 24  # the entry points take at most 2^24 boards, and a level-1 child is a board
@@ -38,7 +39,7 @@ class ExpectimaxActionFunction(LookaheadActionFunction):
 
     ``plies=1`` is the parent (same outputs); ``plies=2`` the pipeline above; anything else raises ``ValueError``.
     ``policy_fn(boards, masks) -> (q2 f32 [B,4], v f32 [B])`` with the parent's shapes and masking, ``use_mask=True,
-    sample_actions=False`` forced, the same un-batched ``__call__``.  ``dedup=False`` skips the dedup launch and values every
+    sample_actions=False`` forced, ``QPlayer``'s un-batched ``__call__``.  ``dedup=False`` skips the dedup launch and values every
     afterstate's children.  ``max_children``: rows per value-forward call AND level-1 children per slice of roots (whole boards;
     a board has at most 120, hence ``max_children >= 120``): the largest input stays bounded in memory and inside the int32
     offsets.  ``last_children`` is the number of value-forward rows of the latest call, ``last_children_full`` that number without
@@ -80,16 +81,9 @@ class ExpectimaxActionFunction(LookaheadActionFunction):
             out = super().policy_fn(boards, masks)
             self.last_children_full = self.last_children
             return out
-        boards = boards.contiguous()
-        B, dev = boards.shape[0], boards.device
-        after1 = torch.empty((B, 4, 16), dtype=torch.uint8, device=dev)
-        reward1 = torch.empty((B, 4), dtype=torch.float32, device=dev)
-        nchild1 = torch.empty((B, 4), dtype=torch.int32, device=dev)
-        nv.lookahead_expand(boards, after1, reward1, nchild1)
-        incl1 = torch.cumsum(nchild1.view(-1), 0, dtype=torch.int32)
-        offset1 = (incl1 - nchild1.view(-1)).view(B, 4)
+        after1, reward1, nchild1, offset1, incl1 = expand_level(boards.contiguous())
         per_board = incl1[3::4].tolist()  # host read 1: the level-1 totals, per board so that the slices can be cut
-        q2 = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        q2 = torch.empty_like(reward1)
         rows = rows_full = 0
         for b0, b1 in self._slices(per_board):
             base = per_board[b0 - 1] if b0 else 0
@@ -98,9 +92,7 @@ class ExpectimaxActionFunction(LookaheadActionFunction):
             rows += n2
             rows_full += n2_full
         self.last_children, self.last_children_full = rows, rows_full
-        legal = nchild1 > 0
-        v = torch.where(legal, q2, torch.full_like(q2, float("-inf"))).max(dim=1).values
-        return q2, torch.where(legal.any(dim=1), v, torch.zeros_like(v))
+        return q2, self.best_legal(q2, nchild1 > 0)
 
     policy_fn.needs_masks = False
 
@@ -110,13 +102,8 @@ class ExpectimaxActionFunction(LookaheadActionFunction):
         if N1 == 0:  # nothing but terminal boards
             q2.zero_()
             return 0, 0
-        children1 = torch.empty((N1, 16), dtype=torch.uint8, device=dev)
-        terminal1 = torch.empty(N1, dtype=torch.uint8, device=dev)
-        nv.lookahead_children(after1, nchild1, offset1, N1, children1, terminal1)
-        after2 = torch.empty((N1, 4, 16), dtype=torch.uint8, device=dev)
-        reward2 = torch.empty((N1, 4), dtype=torch.float32, device=dev)
-        nchild2 = torch.empty((N1, 4), dtype=torch.int32, device=dev)
-        nv.lookahead_expand(children1, after2, reward2, nchild2)
+        children1, terminal1 = spawn_children(after1, nchild1, offset1, N1)
+        after2, reward2, nchild2 = expand(children1)  # (scanned below: the dedup decides which counts)
         if self.dedup:
             group_start = torch.empty(G + 1, dtype=torch.int32, device=dev)
             group_start[:G] = offset1[:, 0] * 4
@@ -127,19 +114,13 @@ class ExpectimaxActionFunction(LookaheadActionFunction):
         else:
             rep = torch.arange(4 * N1, dtype=torch.int32, device=dev).view(N1, 4)
             nuniq = nchild2
-        incl2 = torch.cumsum(nuniq.view(-1), 0, dtype=torch.int32)
-        offset2 = (incl2 - nuniq.view(-1)).view(N1, 4)
+        offset2, incl2 = scan(nuniq)
         if self.dedup:
             N2, N2_full = torch.stack((incl2[-1], nchild2.sum(dtype=torch.int32))).tolist()  # host read 2
         else:
             N2 = N2_full = int(incl2[-1].item())
-        children2 = torch.empty((N2, 16), dtype=torch.uint8, device=dev)
-        terminal2 = torch.empty(N2, dtype=torch.uint8, device=dev)
-        values = torch.empty(N2, dtype=torch.float32, device=dev)
-        nv.lookahead_children(after2, nuniq, offset2, N2, children2, terminal2)
-        for c0 in range(0, N2, self._chunk):
-            c1 = min(N2, c0 + self._chunk)
-            values[c0:c1] = self._values(children2[c0:c1]).to(torch.float32).reshape(-1)
+        children2, terminal2 = spawn_children(after2, nuniq, offset2, N2)
+        values = self.values(children2)
         e = torch.empty((N1, 4), dtype=torch.float32, device=dev)
         nv.lookahead_reduce(torch.zeros_like(reward2), nuniq, offset2, values, terminal2, self.gamma, N2, e)
         v1 = torch.empty(N1, dtype=torch.float32, device=dev)

@@ -7,22 +7,66 @@ cells of the afterstate, tile 2 with p = 0.9, tile 4 with p = 0.1), so the expec
 lock-step: ``g2048_lookahead_expand`` (four afterstates per board) -> ``torch.cumsum`` over the 4 B child counts, whose total
 is read back once (the children have to be sized for the forward) -> ``g2048_lookahead_children`` -> the agent's value
 forward on the children, in chunks of ``max_children`` rows -> ``g2048_lookahead_reduce``.
+
+The steps are functions of this module, shared with the two-ply player (``expectimax.py``) and the probes: ``expand_level`` (expand and
+scan, no host read), ``spawn_children``, and ``LookaheadActionFunction.values``, the chunked critic forward that the Monte-Carlo
+player bootstraps from as well.  The un-batched ``__call__`` and the masked max are ``QPlayer``'s (``q_player.py``).
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
-import numpy as np
 import torch
 
-from ..actions import _common as C
-from ..env_definitions import BOARD_FLAT_DIM, OBS_DIM
 from ..g2048 import native as nv
+from .q_player import QPlayer
 from .torch_action_wrapper import TorchActionFunction
 
 
-class LookaheadActionFunction(TorchActionFunction):
-    """``TorchActionFunction`` whose "logits" are the one-ply expectimax values ``Q(s, .)`` of the agent's critic.
+class Level(NamedTuple):
+    """One expansion level of n boards: the four afterstates, their merge scores, the spawn children behind each move (0 where it
+    is illegal), where a move's children start in the packed child rows, and the inclusive scan (its last entry is their number)."""
+    after: torch.Tensor  # u8 [n, 4, 16]
+    reward: torch.Tensor  # f32 [n, 4]
+    nchild: torch.Tensor  # i32 [n, 4]
+    offset: torch.Tensor  # i32 [n, 4]
+    incl: torch.Tensor  # i32 [4 n]
+
+
+def expand(boards: torch.Tensor):
+    """boards u8 [n, 16] (contiguous) -> (after, reward, nchild) of ``g2048_lookahead_expand``, newly allocated."""
+    n, dev = boards.shape[0], boards.device
+    after = torch.empty((n, 4, 16), dtype=torch.uint8, device=dev)
+    reward = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    nchild = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    nv.lookahead_expand(boards, after, reward, nchild)
+    return after, reward, nchild
+
+
+def scan(counts: torch.Tensor):
+    """counts i32 [n, 4] -> (offset i32 [n, 4], incl i32 [4 n]): the exclusive and the inclusive prefix sum, on the device."""
+    incl = torch.cumsum(counts.view(-1), 0, dtype=torch.int32)
+    return (incl - counts.view(-1)).view(-1, 4), incl
+
+
+def expand_level(boards: torch.Tensor) -> Level:
+    """``expand`` and the ``scan`` of its child counts; no host read (the caller reads ``incl`` to size the children)."""
+    after, reward, nchild = expand(boards)
+    return Level(after, reward, nchild, *scan(nchild))
+
+
+def spawn_children(after: torch.Tensor, counts: torch.Tensor, offset: torch.Tensor, N: int):
+    """Every spawn child of every afterstate, packed at ``offset`` -> (children u8 [N, 16], terminal u8 [N])."""
+    dev = after.device
+    children = torch.empty((N, 16), dtype=torch.uint8, device=dev)
+    terminal = torch.empty(N, dtype=torch.uint8, device=dev)
+    nv.lookahead_children(after, counts, offset, N, children, terminal)
+    return children, terminal
+
+
+class LookaheadActionFunction(QPlayer, TorchActionFunction):
+    """``TorchActionFunction`` whose "logits" are the one-ply expectimax values ``Q(s, .)`` of the agent's critic, played as a
+    ``QPlayer`` (its un-batched ``__call__``; ``rng_mode`` may be a string, an unknown one raises ``ValueError`` when it is used).
 
     ``policy_fn(boards, masks)`` returns ``(q f32 [B, 4], v f32 [B])`` with ``v = max over the legal actions of q`` (0 where
     there is none).  ``use_mask=True, sample_actions=False`` are forced, so the engine (``g2048_policy_step``) takes the
@@ -73,50 +117,23 @@ class LookaheadActionFunction(TorchActionFunction):
         """Boards per ``_values`` call: ``max_children`` counts forward rows, and the ensemble makes eight of a board."""
         return max(1, self.max_children // 8) if self.symmetry == "ensemble" else self.max_children
 
+    def values(self, rows: torch.Tensor) -> torch.Tensor:
+        """The critic on any number of packed boards u8 [n, 16] -> f32 [n], ``_chunk`` boards per ``_values`` call."""
+        n = rows.shape[0]
+        out = torch.empty(n, dtype=torch.float32, device=rows.device)
+        for c0 in range(0, n, self._chunk):
+            c1 = min(n, c0 + self._chunk)
+            out[c0:c1] = self._values(rows[c0:c1]).to(torch.float32).reshape(-1)
+        return out
+
     @torch.no_grad()
     def policy_fn(self, boards: torch.Tensor, masks: torch.Tensor = None):
         """boards u8 [B, 16], masks unused (legality comes out of the expansion) -> (q f32 [B, 4], v f32 [B])."""
-        boards = boards.contiguous()
-        B, dev = boards.shape[0], boards.device
-        after = torch.empty((B, 4, 16), dtype=torch.uint8, device=dev)
-        reward = torch.empty((B, 4), dtype=torch.float32, device=dev)
-        nchild = torch.empty((B, 4), dtype=torch.int32, device=dev)
-        nv.lookahead_expand(boards, after, reward, nchild)
-        incl = torch.cumsum(nchild.view(-1), 0, dtype=torch.int32)
-        offset = (incl - nchild.view(-1)).view(B, 4)
+        after, reward, nchild, offset, incl = expand_level(boards.contiguous())
         N = self.last_children = int(incl[-1].item())  # the one host read of the lock-step
-        children = torch.empty((N, 16), dtype=torch.uint8, device=dev)
-        terminal = torch.empty(N, dtype=torch.uint8, device=dev)
-        values = torch.empty(N, dtype=torch.float32, device=dev)
-        nv.lookahead_children(after, nchild, offset, N, children, terminal)
-        for c0 in range(0, N, self._chunk):
-            c1 = min(N, c0 + self._chunk)
-            values[c0:c1] = self._values(children[c0:c1]).to(torch.float32).reshape(-1)
-        q = torch.empty((B, 4), dtype=torch.float32, device=dev)
-        nv.lookahead_reduce(reward, nchild, offset, values, terminal, self.gamma, N, q)
-        legal = nchild > 0
-        v = torch.where(legal, q, torch.full_like(q, float("-inf"))).max(dim=1).values
-        return q, torch.where(legal.any(dim=1), v, torch.zeros_like(v))
+        children, terminal = spawn_children(after, nchild, offset, N)
+        q = torch.empty_like(reward)
+        nv.lookahead_reduce(reward, nchild, offset, self.values(children), terminal, self.gamma, N, q)
+        return q, self.best_legal(q, nchild > 0)
 
     policy_fn.needs_masks = False
-
-    @torch.no_grad()
-    def __call__(self, rng_key, obs, mask):
-        """Un-batched plug-in protocol ``(rng_key[2], obs[4,4,31], mask[4]) -> (action, log_prob, value)``; leading batch
-        dimensions are accepted.  The one-hot observation is decoded to a packed board and goes down ``policy_fn``."""
-        obs_t = torch.as_tensor(np.asarray(obs.cpu() if isinstance(obs, torch.Tensor) else obs))
-        batched = obs_t.ndim > 3
-        dev = C.device()
-        boards = obs_t.reshape(-1, BOARD_FLAT_DIM, OBS_DIM).to(torch.float32).argmax(dim=-1).to(torch.uint8).to(dev)
-        q, values = self.policy_fn(boards, None)
-        bits = C.mask_to_bits(mask)
-        keys = C.keys_tensor(rng_key)
-        n = bits.numel()
-        actions = torch.empty(n, dtype=torch.int32, device=dev)
-        logp = torch.empty(n, dtype=torch.float32, device=dev)
-        mode = C.default_rng_mode() if self.rng_mode is None else self.rng_mode
-        nv.act_logits(keys, q.contiguous(), bits, True, False, actions, logp, mode)
-        a, lp, v = actions.cpu().numpy(), logp.cpu().numpy(), values.cpu().numpy()
-        if batched:
-            return a, lp, v
-        return np.int32(a[0]), np.float32(lp[0]), np.float32(v[0])

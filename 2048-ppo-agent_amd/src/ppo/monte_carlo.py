@@ -6,7 +6,8 @@ For every root board and every legal move, R playouts of a cheap policy (uniform
 afterstate; the move with the best mean return is played.  The playouts run in ``g2048_mc_playout``: one lane per playout, lane
 ``(4 b + a) R + r``, the board in registers across a launch of up to 128 steps, no trajectory written; ``g2048_mc_reduce`` sums
 each pair's R lanes in ascending order.  Without an agent no network is touched; with one, the playouts are cut off after
-``depth`` steps and the agent's critic values the leaves (``4 R`` value-forward rows per board).
+``depth`` steps and the agent's critic values the leaves (``4 R`` value-forward rows per board).  How the scores become moves
+(the un-batched ``__call__``, the rng mode, the masked max) is ``QPlayer``'s (``q_player.py``).
 """
 from __future__ import annotations
 
@@ -15,21 +16,20 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ..actions import _common as C
-from ..env_definitions import BOARD_FLAT_DIM, OBS_DIM
 from ..g2048 import native as nv
 from ..g2048.engine import seed_key
+from .q_player import QPlayer
 from .torch_action_wrapper import resolve_symmetry
 
 PLAYOUT_POLICIES = {"random": "POLICY_RANDOM", "drul": "POLICY_DRUL"}
 
 
-class MonteCarloActionFunction:
+class MonteCarloActionFunction(QPlayer):
     """``act_fn`` plug-in for ``BatchRunner`` whose "logits" are Monte-Carlo estimates ``Q(s, .)`` of the playout returns.
 
     ``policy_fn(boards, masks)`` returns ``(q f32 [B, 4], v f32 [B])`` with ``v = max over the legal actions of q`` (0 where
-    there is none; ``q`` of an illegal action is +0).  ``use_mask=True, sample_actions=False`` are forced, so the engine
-    (``g2048_policy_step``) takes the masked argmax of ``q``; the env, its key stream and the trajectory format are untouched.
+    there is none; ``q`` of an illegal action is +0).  ``use_mask=True, sample_actions=False`` are forced (``QPlayer``), so the
+    engine (``g2048_policy_step``) takes the masked argmax of ``q``; the env, its key stream and the trajectory format are untouched.
     The recorded ``log_prob`` is therefore the log-softmax of scores at the chosen action: NOT a policy probability (``q`` is in
     score units), so such trajectories are for evaluation only, not for a PPO update.
 
@@ -37,8 +37,9 @@ class MonteCarloActionFunction:
     per playout, the root move included; ``None`` plays until every lane has terminated (launches of at most 128 steps, the live
     counter read once per launch; more than ``max_steps`` steps raise ``RuntimeError``); ``depth=d`` runs ``ceil(d / 128)`` launches
     and reads nothing back.  ``gamma``: discount, default 0.99 with an agent and 1.0 without.  ``agent``: its critic values the leaf
-    boards (the value forward of ``LookaheadActionFunction._values``, in chunks of ``max_children`` rows, ``symmetry`` and
-    ``amp_dtype`` as there); ``None``: plain playout returns.
+    boards (the value forward of ``LookaheadActionFunction.values``, in chunks of ``max_children`` rows, ``symmetry`` and
+    ``amp_dtype`` as there); ``None``: plain playout returns.  ``rng_mode``: anything ``resolve_rng_mode`` takes; an unknown
+    spelling raises ``ValueError`` at the first call (it used to mean "partitionable").
     The playout keys are a chain of their own, seeded by ``seed`` and advanced by two sub-keys per playout step
     (``g2048_chain_keys``): independent of the env's stream, deterministic in ``seed`` and the sequence of calls.  The roots of a
     call are cut into slices of whole boards with ``4 R B_slice <= max_lanes``; every slice draws the keys of the uncut call, so
@@ -46,8 +47,6 @@ class MonteCarloActionFunction:
     latest call.
     """
 
-    use_mask = True
-    sample_actions = False
     compact = True
 
     def __init__(self, agent=None, playouts: int = 32, depth: Optional[int] = None, playout_policy: str = "random",
@@ -92,17 +91,10 @@ class MonteCarloActionFunction:
         self.last_lanes = 0
 
     # ------------------------------------------------------------------ playouts
-    def _mode(self) -> int:
-        if self.rng_mode is None:
-            return C.default_rng_mode()
-        if isinstance(self.rng_mode, str):  # the spellings BatchRunner takes
-            return nv.RNG_LEGACY if self.rng_mode.lower() in ("legacy", "0") else nv.RNG_PARTITIONABLE
-        return int(self.rng_mode)
-
     def _launch_subs(self, cache: list, k: int, n_steps: int) -> np.ndarray:
         """Sub-keys [n_steps, 4] of launch k of this call; drawn from the chain the first time a slice asks for them."""
         while len(cache) <= k:
-            self._key, subs = nv.chain_keys(self._key, 2 * n_steps, self._mode())
+            self._key, subs = nv.chain_keys(self._key, 2 * n_steps, self._rng_mode())
             cache.append(subs.reshape(n_steps, 4))
         return cache[k]
 
@@ -122,7 +114,7 @@ class MonteCarloActionFunction:
             subs = self._launch_subs(cache, k, n_steps)
             if live is not None:
                 live.zero_()
-            nv.mc_playout(subs, t, roots, Bs, R, lane0, n_total, policy, self.gamma, *state, self._mode(), live)
+            nv.mc_playout(subs, t, roots, Bs, R, lane0, n_total, policy, self.gamma, *state, self._rng_mode(), live)
             t += n_steps
             k += 1
             if live is not None and int(live.item()) == 0:  # the one host read of the launch
@@ -156,38 +148,10 @@ class MonteCarloActionFunction:
         if B == 0:
             return q, torch.empty(0, dtype=torch.float32, device=dev)
         for b0, b1, (lb, lm, ld, lret, ldisc) in self.playout(boards):
-            values = None
-            if self._critic is not None:
-                n = lb.shape[0]
-                values = torch.empty(n, dtype=torch.float32, device=dev)
-                chunk = self._critic._chunk
-                for c0 in range(0, n, chunk):
-                    c1 = min(n, c0 + chunk)
-                    values[c0:c1] = self._critic._values(lb[c0:c1]).to(torch.float32).reshape(-1)
+            values = None if self._critic is None else self._critic.values(lb)
             nv.mc_reduce(lret, ldisc, ld, values, R, q[b0:b1])
             # a legal root move changes the board (and a tile is spawned); the lane of an illegal one still holds the root
             legal[b0:b1] = (lb.view(b1 - b0, 4, R, 16)[:, :, 0] != boards[b0:b1, None]).any(dim=-1)
-        v = torch.where(legal, q, torch.full_like(q, float("-inf"))).max(dim=1).values
-        return q, torch.where(legal.any(dim=1), v, torch.zeros_like(v))
+        return q, self.best_legal(q, legal)
 
     policy_fn.needs_masks = False
-
-    @torch.no_grad()
-    def __call__(self, rng_key, obs, mask):
-        """Un-batched plug-in protocol ``(rng_key[2], obs[4,4,31], mask[4]) -> (action, log_prob, value)``; leading batch
-        dimensions are accepted.  The one-hot observation is decoded to a packed board and goes down ``policy_fn``."""
-        obs_t = torch.as_tensor(np.asarray(obs.cpu() if isinstance(obs, torch.Tensor) else obs))
-        batched = obs_t.ndim > 3
-        dev = C.device()
-        boards = obs_t.reshape(-1, BOARD_FLAT_DIM, OBS_DIM).to(torch.float32).argmax(dim=-1).to(torch.uint8).to(dev)
-        q, values = self.policy_fn(boards, None)
-        bits = C.mask_to_bits(mask)
-        keys = C.keys_tensor(rng_key)
-        n = bits.numel()
-        actions = torch.empty(n, dtype=torch.int32, device=dev)
-        logp = torch.empty(n, dtype=torch.float32, device=dev)
-        nv.act_logits(keys, q.contiguous(), bits, True, False, actions, logp, self._mode())
-        a, lp, v = actions.cpu().numpy(), logp.cpu().numpy(), values.cpu().numpy()
-        if batched:
-            return a, lp, v
-        return np.int32(a[0]), np.float32(lp[0]), np.float32(v[0])

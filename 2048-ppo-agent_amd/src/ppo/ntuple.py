@@ -6,7 +6,8 @@ The 2048 literature's standard learner: no matrix engine, one evaluation is ``8 
 The player scores every legal move by ``reward + V(afterstate)`` (``g2048_ntuple_scores``) and the engine takes the masked argmax;
 the trainer learns V by temporal differences between consecutive afterstates of always-live boards, batch-synchronously: all envs
 of a lock-step accumulate into integer tables (``g2048_ntuple_td_accumulate``), every entry that was hit moves by the mean of its
-deltas (``g2048_ntuple_td_apply``).  All accumulation is integer arithmetic, so a run is reproducible bit for bit.
+deltas (``g2048_ntuple_td_apply``).  All accumulation is integer arithmetic, so a run is reproducible bit for bit.  How the scores
+become moves outside the trainer (the un-batched ``__call__``, the rng mode) is ``QPlayer``'s (``q_player.py``).
 """
 from __future__ import annotations
 
@@ -16,9 +17,9 @@ import numpy as np
 import torch
 
 from ..actions import _common as C
-from ..env_definitions import BOARD_FLAT_DIM, OBS_DIM
 from ..g2048 import native as nv
 from ..g2048.engine import seed_key
+from .q_player import QPlayer
 
 DEFAULT_TUPLES = ((0, 1, 2, 3, 4, 5), (4, 5, 6, 7, 8, 9), (0, 1, 2, 4, 5, 6), (4, 5, 6, 8, 9, 10))
 MAX_TUPLES, MAX_CELLS, MAX_FRAC_BITS = 8, 6, 20
@@ -46,14 +47,6 @@ def _check_tuples(tuples) -> np.ndarray:
 
 def _device(device) -> torch.device:
     return C.device() if device is None else torch.device(device)
-
-
-def _mode(rng_mode) -> int:
-    if rng_mode is None:
-        return C.default_rng_mode()
-    if isinstance(rng_mode, str):  # the spellings BatchRunner takes
-        return nv.RNG_LEGACY if rng_mode.lower() in ("legacy", "0") else nv.RNG_PARTITIONABLE
-    return int(rng_mode)
 
 
 class NTupleNetwork:
@@ -103,17 +96,16 @@ class NTupleNetwork:
         return net
 
 
-class NTupleActionFunction:
+class NTupleActionFunction(QPlayer):
     """``act_fn`` plug-in for ``BatchRunner`` whose "logits" are the n-tuple network's afterstate scores.
 
     ``policy_fn(boards, masks)`` returns ``(q f32 [B, 4], v f32 [B])`` of ``NTupleNetwork.scores``.  ``use_mask=True,
-    sample_actions=False`` are forced, so the engine (``g2048_policy_step``) takes the masked argmax of ``q``; the env, its key
-    stream and the trajectory format are untouched.  The recorded ``log_prob`` is the log-softmax of scores at the chosen action:
+    sample_actions=False`` are forced (``QPlayer``), so the engine (``g2048_policy_step``) takes the masked argmax of ``q``; the env,
+    its key stream and the trajectory format are untouched.  The recorded ``log_prob`` is the log-softmax of scores at the chosen action:
     NOT a policy probability (``q`` is in score units), so such trajectories are for evaluation only, not for a PPO update.
+    ``rng_mode``: anything ``resolve_rng_mode`` takes; an unknown spelling raises ``ValueError`` (it used to mean "partitionable").
     """
 
-    use_mask = True
-    sample_actions = False
     compact = True
 
     def __init__(self, network: NTupleNetwork, device=None, rng_mode=None):
@@ -129,26 +121,6 @@ class NTupleActionFunction:
         return self.network.scores(boards)
 
     policy_fn.needs_masks = False
-
-    @torch.no_grad()
-    def __call__(self, rng_key, obs, mask):
-        """Un-batched plug-in protocol ``(rng_key[2], obs[4,4,31], mask[4]) -> (action, log_prob, value)``; leading batch
-        dimensions are accepted.  The one-hot observation is decoded to a packed board and goes down ``policy_fn``."""
-        obs_t = torch.as_tensor(np.asarray(obs.cpu() if isinstance(obs, torch.Tensor) else obs))
-        batched = obs_t.ndim > 3
-        dev = C.device()
-        boards = obs_t.reshape(-1, BOARD_FLAT_DIM, OBS_DIM).to(torch.float32).argmax(dim=-1).to(torch.uint8).to(dev)
-        q, values = self.policy_fn(boards, None)
-        bits = C.mask_to_bits(mask)
-        keys = C.keys_tensor(rng_key)
-        n = bits.numel()
-        actions = torch.empty(n, dtype=torch.int32, device=dev)
-        logp = torch.empty(n, dtype=torch.float32, device=dev)
-        nv.act_logits(keys, q.contiguous(), bits, True, False, actions, logp, _mode(self.rng_mode))
-        a, lp, v = actions.cpu().numpy(), logp.cpu().numpy(), values.cpu().numpy()
-        if batched:
-            return a, lp, v
-        return np.int32(a[0]), np.float32(lp[0]), np.float32(v[0])
 
 
 class NTupleTrainer:
@@ -171,7 +143,7 @@ class NTupleTrainer:
         self.network = network
         self.num_envs = B = int(num_envs)
         self.alpha = float(alpha)
-        self.rng_mode = _mode(rng_mode)
+        self.rng_mode = C.resolve_rng_mode(rng_mode)
         self.device = dev = network.device if device is None else torch.device(device)
         if dev != network.weights.device:
             raise ValueError(f"the trainer's device {dev} is not the network's {network.weights.device}")

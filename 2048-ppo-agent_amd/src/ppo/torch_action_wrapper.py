@@ -10,11 +10,9 @@ from __future__ import annotations
 import os
 from typing import Optional
 
-import numpy as np
 import torch
 
 from ..actions import _common as C
-from ..env_definitions import BOARD_FLAT_DIM, OBS_DIM
 from ..g2048 import native as nv
 from .capture import capture as capture_graph
 
@@ -208,25 +206,14 @@ class TorchActionFunction:
     @torch.no_grad()
     def __call__(self, rng_key, obs, mask):
         """Un-batched plug-in protocol: ``(rng_key[2], obs[4,4,31], mask[4]) -> (action, log_prob, value)``.
-        Leading batch dimensions are accepted.  The draw and the log-prob come from ``g2048_act_logits``."""
-        obs_t = torch.as_tensor(np.asarray(obs.cpu() if isinstance(obs, torch.Tensor) else obs))
-        batched = obs_t.ndim > 3
-        obs_t = obs_t.reshape(-1, BOARD_FLAT_DIM, OBS_DIM).float()
+        Leading batch dimensions are accepted.  The draw and the log-prob come from ``g2048_act_logits`` (the tail shared with
+        the score players, ``actions/_common.act_on_logits``); ``rng_mode`` is read by ``resolve_rng_mode``, so a string works
+        here as it does in ``BatchRunner`` and an unknown one raises ``ValueError``."""
+        obs_t, batched = C.obs_rows(obs)
         dev = C.device()
         if self.symmetry != "none":  # the one-hot observation is decoded to packed boards and goes down policy_fn
             logits, values = self.policy_fn(obs_t.argmax(dim=-1).to(torch.uint8).to(dev), None)
         else:
             agent_dev = next(self.agent.parameters()).device
             logits, values = self.agent(obs_t.to(agent_dev), None)
-        bits = C.mask_to_bits(mask)
-        keys = C.keys_tensor(rng_key)
-        n = bits.numel()
-        actions = torch.empty(n, dtype=torch.int32, device=dev)
-        logp = torch.empty(n, dtype=torch.float32, device=dev)
-        mode = C.default_rng_mode() if self.rng_mode is None else self.rng_mode
-        nv.act_logits(keys, logits.float().to(dev).contiguous(), bits, self.use_mask, self.sample_actions, actions,
-                      logp, mode)
-        a, lp, v = actions.cpu().numpy(), logp.cpu().numpy(), values.float().reshape(-1).cpu().numpy()
-        if batched:
-            return a, lp, v
-        return np.int32(a[0]), np.float32(lp[0]), np.float32(v[0])
+        return C.act_on_logits(rng_key, logits, values, mask, self.use_mask, self.sample_actions, self.rng_mode, batched)

@@ -7,28 +7,17 @@ host between device steps, exactly as user code, with JAX-free key words instead
 """
 from __future__ import annotations
 
-import os
 from dataclasses import dataclass
 from typing import Callable, Optional
 
 import numpy as np
 import torch
 
+from ..actions._common import resolve_rng_mode
 from ..g2048 import native as nv
 from ..g2048.engine import RolloutEngine, Trajectory, mask_bits_to_bool, one_hot_observations
 
 ENV_ID = "2048"
-
-
-def _resolve_rng_mode(rng_mode) -> int:
-    if rng_mode is None:
-        rng_mode = os.environ.get("G2048_RNG_MODE", "partitionable")
-    if isinstance(rng_mode, str):
-        table = {"legacy": nv.RNG_LEGACY, "partitionable": nv.RNG_PARTITIONABLE, "0": 0, "1": 1}
-        if rng_mode.lower() not in table:
-            raise ValueError(f"unknown rng_mode {rng_mode!r}")
-        return table[rng_mode.lower()]
-    return int(rng_mode)
 
 
 @dataclass
@@ -61,7 +50,7 @@ class BatchRunner:
 
     def __init__(self, init_seed: int, act_fn: Callable = None, rng_mode=None, device=None, env0: int = 0,
                  total_envs: Optional[int] = None):
-        self.rng_mode = _resolve_rng_mode(rng_mode)
+        self.rng_mode = resolve_rng_mode(rng_mode)
         self._engine = RolloutEngine(init_seed, self.rng_mode, device)
         self.device = self._engine.device
         self.env0 = int(env0)

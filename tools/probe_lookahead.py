@@ -29,6 +29,7 @@ import torch  # noqa: E402
 
 from src.g2048 import native as nv  # noqa: E402
 from src.ppo import ExpectimaxActionFunction, LookaheadActionFunction, PPOAgent, TorchActionFunction  # noqa: E402
+from src.ppo.lookahead import expand, expand_level, scan, spawn_children  # noqa: E402
 from src.runs import BatchRunner  # noqa: E402
 
 MODEL = dict(observation_dim=31, action_dim=4, hidden_dim=512, d_model=256, nhead=8, num_layers=4, dim_feedforward=1024,
@@ -70,31 +71,14 @@ def probe(agent, B, dev, repeats, symmetry="none"):
     res["children"] = N
     res["children_per_board"] = round(N / B, 2)
     # the parts, on the tensors of one expansion
-    after = torch.empty((B, 4, 16), dtype=torch.uint8, device=dev)
-    reward = torch.empty((B, 4), dtype=torch.float32, device=dev)
-    nchild = torch.empty((B, 4), dtype=torch.int32, device=dev)
-    nv.lookahead_expand(boards, after, reward, nchild)
-    incl = torch.cumsum(nchild.view(-1), 0, dtype=torch.int32)
-    offset = (incl - nchild.view(-1)).view(B, 4)
-    children = torch.empty((N, 16), dtype=torch.uint8, device=dev)
-    terminal = torch.empty(N, dtype=torch.uint8, device=dev)
-    values = torch.empty(N, dtype=torch.float32, device=dev)
-    q = torch.empty((B, 4), dtype=torch.float32, device=dev)
-    nv.lookahead_children(after, nchild, offset, N, children, terminal)
-
-    def scan():
-        c = torch.cumsum(nchild.view(-1), 0, dtype=torch.int32)
-        (c - nchild.view(-1)).view(B, 4)
-        return int(c[-1].item())
-
-    def forward():
-        for c0 in range(0, N, look._chunk):
-            values[c0:c0 + look._chunk] = look._values(children[c0:c0 + look._chunk])
-
+    after, reward, nchild, offset, _ = expand_level(boards)
+    children, terminal = spawn_children(after, nchild, offset, N)
+    values = look.values(children)
+    q = torch.empty_like(reward)
     parts = {"expand": timed(lambda: nv.lookahead_expand(boards, after, reward, nchild), repeats),
-             "scan_and_host_read": timed(scan, repeats),
+             "scan_and_host_read": timed(lambda: int(scan(nchild)[1][-1].item()), repeats),
              "children": timed(lambda: nv.lookahead_children(after, nchild, offset, N, children, terminal), repeats),
-             "value_forward": timed(forward, repeats),
+             "value_forward": timed(lambda: look.values(children), repeats),
              "reduce": timed(lambda: nv.lookahead_reduce(reward, nchild, offset, values, terminal, look.gamma, N, q), repeats)}
     res["parts"] = parts
     kernels = sum(parts[k]["median_ms"] for k in ("expand", "children", "reduce"))
@@ -114,58 +98,35 @@ def probe2(agent, B, dev, repeats, dedup, symmetry="none"):
            "lockstep": timed(lambda: fn.policy_fn(boards, None), repeats)}
     res["rows"], res["rows_full"] = fn.last_children, fn.last_children_full
     res["rows_over_rows_full"] = round(fn.last_children / max(fn.last_children_full, 1), 4)
-    i32, u8, f32 = torch.int32, torch.uint8, torch.float32
-    after1 = torch.empty((B, 4, 16), dtype=u8, device=dev)
-    reward1 = torch.empty((B, 4), dtype=f32, device=dev)
-    nchild1 = torch.empty((B, 4), dtype=i32, device=dev)
-    nv.lookahead_expand(boards, after1, reward1, nchild1)
-    incl1 = torch.cumsum(nchild1.view(-1), 0, dtype=i32)
-    offset1 = (incl1 - nchild1.view(-1)).view(B, 4)
+    i32, f32 = torch.int32, torch.float32
+    after1, reward1, nchild1, offset1, incl1 = expand_level(boards)
     N1 = int(incl1[-1].item())
     if N1 > fn.max_children:
         raise SystemExit(f"{B} boards have {N1} level-1 children: more than one slice of {fn.max_children}; probe a smaller batch")
     res["level1_children"] = N1
-    children1 = torch.empty((N1, 16), dtype=u8, device=dev)
-    terminal1 = torch.empty(N1, dtype=u8, device=dev)
-    nv.lookahead_children(after1, nchild1, offset1, N1, children1, terminal1)
-    after2 = torch.empty((N1, 4, 16), dtype=u8, device=dev)
-    reward2 = torch.empty((N1, 4), dtype=f32, device=dev)
-    nchild2 = torch.empty((N1, 4), dtype=i32, device=dev)
-    nv.lookahead_expand(children1, after2, reward2, nchild2)
+    children1, terminal1 = spawn_children(after1, nchild1, offset1, N1)
+    after2, reward2, nchild2 = expand(children1)
     group_start = torch.cat([offset1[:, 0] * 4, torch.tensor([4 * N1], dtype=i32, device=dev)]).to(i32)
     rep = torch.arange(4 * N1, dtype=i32, device=dev).view(N1, 4)
     nuniq = nchild2.clone()
     if dedup:
         nv.lookahead_dedup(after2, nchild2, group_start, rep, nuniq)
-    incl2 = torch.cumsum(nuniq.view(-1), 0, dtype=i32)
-    offset2 = (incl2 - nuniq.view(-1)).view(N1, 4)
+    offset2, incl2 = scan(nuniq)
     N2 = int(incl2[-1].item())
     assert N2 == fn.last_children
-    children2 = torch.empty((N2, 16), dtype=u8, device=dev)
-    terminal2 = torch.empty(N2, dtype=u8, device=dev)
-    values = torch.empty(N2, dtype=f32, device=dev)
-    nv.lookahead_children(after2, nuniq, offset2, N2, children2, terminal2)
+    children2, terminal2 = spawn_children(after2, nuniq, offset2, N2)
+    values = fn.values(children2)
     zero2 = torch.zeros_like(reward2)
     e = torch.empty((N1, 4), dtype=f32, device=dev)
     v1 = torch.empty(N1, dtype=f32, device=dev)
     q2 = torch.empty((B, 4), dtype=f32, device=dev)
 
-    def scan1():
-        c = torch.cumsum(nchild1.view(-1), 0, dtype=i32)
-        (c - nchild1.view(-1)).view(B, 4)
-        return c[3::4].tolist()
-
     def scan2():
-        c = torch.cumsum(nuniq.view(-1), 0, dtype=i32)
-        (c - nuniq.view(-1)).view(N1, 4)
+        c = scan(nuniq)[1]
         return torch.stack((c[-1], nchild2.sum(dtype=i32))).tolist() if dedup else int(c[-1].item())
 
-    def forward():
-        for c0 in range(0, N2, fn._chunk):
-            values[c0:c0 + fn._chunk] = fn._values(children2[c0:c0 + fn._chunk])
-
     parts = {"expand1": timed(lambda: nv.lookahead_expand(boards, after1, reward1, nchild1), repeats),
-             "scan1_and_host_read": timed(scan1, repeats),
+             "scan1_and_host_read": timed(lambda: scan(nchild1)[1][3::4].tolist(), repeats),
              "children1": timed(lambda: nv.lookahead_children(after1, nchild1, offset1, N1, children1, terminal1), repeats),
              "expand2": timed(lambda: nv.lookahead_expand(children1, after2, reward2, nchild2), repeats)}
     if dedup:
@@ -173,7 +134,7 @@ def probe2(agent, B, dev, repeats, dedup, symmetry="none"):
     parts.update({
         "scan2_and_host_read": timed(scan2, repeats),
         "children2": timed(lambda: nv.lookahead_children(after2, nuniq, offset2, N2, children2, terminal2), repeats),
-        "value_forward": timed(forward, repeats),
+        "value_forward": timed(lambda: fn.values(children2), repeats),
         "reduce2": timed(lambda: nv.lookahead_reduce(zero2, nuniq, offset2, values, terminal2, fn.gamma, N2, e), repeats),
         "backup": timed(lambda: nv.lookahead_backup(reward2, nchild2, rep, e, v1), repeats),
         "reduce1": timed(lambda: nv.lookahead_reduce(reward1, nchild1, offset1, v1, terminal1, fn.gamma, N1, q2), repeats)})
