@@ -304,6 +304,7 @@ extern "C" int g2048_add_ln_bwd(const float *x_norm, int64_t x_row_stride, const
                                 const float *rstd, const float *gamma, float *dx, void *da, float *dparams, float *workspace,
                                 int64_t T, float p_drop, uint64_t seed, const uint64_t *seed_state, int g_x_period, void *stream) {
     if (g_x_period < 1) return G2048_EINVAL;
+    if (g_x && T % g_x_period != 0) return G2048_EINVAL;  // g_x is [T / g_x_period][256]: the row period * (T / period) would lie behind it
     if (!g_h || !dx || !workspace || T <= 0 || (x_row_stride & 3) || (gamma && (!x_norm || !mean || !rstd)) ||
         !(p_drop >= 0.f && p_drop < 1.f) || !aligned16(x_norm, g_x, dx, gamma) ||
         (((uintptr_t)g_h | (uintptr_t)da) & 7))

@@ -503,6 +503,9 @@ extern "C" int g2048_linear_add_ln_bwd(const void *dy, int64_t lddy, const void 
         !(p_drop >= 0.f && p_drop < 1.f) || (x_row_stride & 3) ||
         !aligned16(x_norm, g_x, gamma, dx) || ((uintptr_t)da & 7) || ((uintptr_t)partial & 3))
         return G2048_EINVAL;
+    // g_x is [T / g_x_period][256], g_h_extra [T / extra_period][256]: with a remainder the token row period * (T / period) would read
+    // the row behind the buffer
+    if ((g_x && T % g_x_period != 0) || (g_h_extra && T % extra_period != 0)) return G2048_EINVAL;
     RowGemmArgs A{};
     A.x = (const __bf16 *)dy; A.ldx = lddy; A.w = (const __bf16 *)wt_packed; A.T = T; A.K = K;
     A.w_tile_stride = wt_tile_stride; A.gh_extra = (const uint16_t *)g_h_extra; A.extra_period = extra_period < 1 ? 1 : extra_period;

@@ -470,7 +470,8 @@ int g2048_add_ln_fwd(const float *x, int64_t x_row_stride, const void *a, const 
                      uint64_t seed, const uint64_t *seed_state, void *stream);
 /* x_norm = the tensor that was normalised (x_new, or x when a was NULL); g_x f32 or NULL = gradient arriving on x_new from
  * the residual stream: [T][256] with g_x_period 1, or only for every g_x_period-th token row ([T / g_x_period][256], e.g.
- * period 17 = the CLS rows of [B][17][256], all the last encoder layer hands back); g_h bf16 [T][256].  dx f32 [T][256] = g_x + dLayerNorm (gradient for x);
+ * period 17 = the CLS rows of [B][17][256], all the last encoder layer hands back; T must then be a multiple of g_x_period, otherwise
+ * G2048_EINVAL: the token row g_x_period * (T / g_x_period) would read behind g_x); g_h bf16 [T][256].  dx f32 [T][256] = g_x + dLayerNorm (gradient for x);
  * da bf16 [T][256] or NULL = dropout-masked dx (gradient for a); dparams f32 [3][256] = dgamma, dbeta and the column
  * sums of da (= the bias gradient of the Linear that produced a; zeros when da is NULL), summed in a fixed order;
  * workspace: g2048_add_ln_bwd_workspace_floats(T) floats of scratch.  dparams NULL: first stage only, the workspace then
@@ -499,7 +500,8 @@ int g2048_linear_add_ln_fwd(const void *u, int64_t ldu, const void *w_packed, co
  * packed matrix [256][K'] (point at the first k-step and pass wt_tile_stride = (K' / 16) * 512, the distance in elements between its
  * 32-row tiles; 0 = dense): the K/V rows of a packed in_proj^T.  g_h_extra (bf16 [T / extra_period][256] or NULL) is added to g_h on
  * the rows tok % extra_period == 0 (rounded to bf16 again, as an addmm into the bf16 gradient would): the CLS rows' share of the
- * last layer's query projection.  da may be NULL (the LayerNorm had no branch); partial: f32
+ * last layer's query projection.  G2048_EINVAL when g_x is given and T is no multiple of g_x_period, or g_h_extra is given and T is no
+ * multiple of extra_period (the last token row of that kind would read behind the buffer).  da may be NULL (the LayerNorm had no branch); partial: f32
  * [g2048_linear_add_ln_bwd_partial_rows(T)][3][256] first-stage sums (dgamma | dbeta | column sums of da) for g2048_reduce_jobs. */
 int64_t g2048_linear_add_ln_bwd_partial_rows(int64_t T);
 int g2048_linear_add_ln_bwd(const void *dy, int64_t lddy, const void *wt_packed, int64_t wt_tile_stride, int K, const float *x_norm,

@@ -98,7 +98,9 @@ def rounding_shares(v):
     """-> (share of the values that are no bf16 numbers, share that lie exactly between two bf16 neighbours)."""
     r = f64(v).abs()
     _, e = torch.frexp(r)  # r = m 2^e, m in [0.5, 1): the bf16 spacing at r is 2^(e - 8)
-    q = torch.ldexp(r, 8 - e)
+    # 2^(8 - e) built from its exponent bits, exact on every device.  (torch.ldexp did not scale exactly there: on the MI355X this
+    # function reported 100 % of the integers around 3000 of a K = 768 product as needing rounding and no tie, where the CPU counts 94 % and 6.7 %.)
+    q = r * ((8 - e).to(torch.int64) + 1023 << 52).view(F64)
     frac = q - q.floor()
     return (frac != 0).double().mean().item(), (frac == 0.5).double().mean().item()
 

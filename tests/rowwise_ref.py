@@ -232,9 +232,11 @@ def add_ln_fwd_check(x, a, gamma, beta, eps, p, seed, seed_state, x_new, h, mean
     return out + ln_check(v, gamma, beta, eps, h, mean, rstd, "A2", "A3", fig)
 
 
-def add_ln_bwd_check(xn, g_x, period, g_h, mean, rstd, gamma, p, seed, seed_state, dx, da, sums, rows_per_group=None, fig=None, tier_a=False):
+def add_ln_bwd_check(xn, g_x, period, g_h, mean, rstd, gamma, p, seed, seed_state, dx, da, sums, rows_per_group=None, fig=None, tier_a=False,
+                     gid=None):
     """xn f32 [T, 256] (None without gamma); g_x f32 [T / period, 256] or None; sums: dparams [3, 256] (``rows_per_group`` None) or the
-    workspace partials [groups, 768]."""
+    workspace partials [groups, 768].  ``gid`` = (long [T]: the group of every row, the number of groups) replaces the consecutive
+    blocks of ``rows_per_group`` rows (the fused kernel of tests/rowgemm_ref.py, whose workgroups walk tiles)."""
     T, dev, out = g_h.shape[0], g_h.device, []
     zero = torch.zeros((), dtype=F64, device=dev)
     gh = gr.f64(g_h)
@@ -261,7 +263,11 @@ def add_ln_bwd_check(xn, g_x, period, g_h, mean, rstd, gamma, p, seed, seed_stat
     if da is not None:
         out += exact(da, scaled_bf16(dx, inv_of(p), row_keep(seed, seed_state, T, p, dev)), "A5 da", fig)
         written = gr.f64(da)
-    gid, G, n = _gid(T, rows_per_group, dev)
+    if gid is None:
+        gid, G, n = _gid(T, rows_per_group, dev)
+    else:
+        gid, G = gid
+        n = torch.bincount(gid, minlength=G)
     got = sums.reshape(G, 3, D)
     for k, (name, terms, extra) in enumerate((("dgamma", gh * xh, gh.abs() * Exh), ("dbeta", gh, None), ("da sums", written, None))):
         out += sums_check(got[:, k], terms, extra, gid, G, n, f"A6 {name}", fig, tier_a)
