@@ -35,15 +35,20 @@
 // f32 LayerNorm / softmax statistics.
 //
 // Two-kernel form (when the caller passes a workspace).  Only the CLS row of the LAST layer is read by the "cls"
-// reduction.  k_encoder_main<HEAD> runs layers 0..L-2, then only LayerNorm + the K/V projections of layer L-1, and
-// parks K, V (bf16, 17 KB per board) and the CLS residual row in HBM.  k_encoder_tail batches the CLS tokens of 128
-// boards per workgroup (one board per lane) through the rest of layer L-1: Q projection, attention of that single query
-// over its board's 17 keys in-lane (K/V from HBM), out-proj, feed-forward.
+// reduction.  k_encoder_main<CLS> runs layers 0..L-2, then of layer L-1 only LayerNorm, the K/V projections and the
+// attention of each board's CLS query over its 17 keys (K and V never leave the chip: Q of the 7 CLS columns is one extra
+// product per head on one wave, scores / softmax / P.V run on the vector ALU under the K/V chains), and leaves the CLS
+// row's attention output (bf16, 512 B per board) and its residual row (f32, 1 KiB) in HBM.  k_encoder_tail<false> batches
+// the CLS tokens of 128 boards per workgroup (one board per lane) through the rest of layer L-1: out-proj, feed-forward.
+// G2048_ENCODER_KV_WS=1 selects the earlier shape of the pair, the A/B arm that gives the same bits: k_encoder_main<HEAD>
+// parks K, V (bf16, 17 KB per board) in HBM and k_encoder_tail<true> projects Q and attends in-lane over K/V read back.
 //
 // "mean" reduction (g2048_policy_encoder_mean): k_encoder_main<MEAN> runs every layer in full like <FULL>; its epilogue stages
 // the board tokens' final residual rows in LDS and averages the 16 rows of each board in a fixed order.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/g2048.h"
 #include "g2048_host.h"
@@ -276,9 +281,12 @@ __device__ __forceinline__ void layer_norm(const f32x16 r[8], bf16x8 out[16]) {
 }
 
 // MODE_MEAN: all layers full, like MODE_FULL, then the "mean" reduction (the 16 board tokens averaged) instead of the CLS rows
-constexpr int MODE_FULL = 0, MODE_HEAD = 1, MODE_MEAN = 2;
-// HBM workspace of the two-kernel form, per board: K and V of the last layer as [head][key][lane half][16] bf16 (the 16
-// values a lane half holds for one (token, head) are contiguous), then the CLS residual row (256 f32).
+// MODE_CLS: the two-kernel form; MODE_HEAD: its earlier shape, which parks the last layer's K/V in HBM (the A/B arm, G2048_ENCODER_KV_WS=1)
+constexpr int MODE_FULL = 0, MODE_HEAD = 1, MODE_MEAN = 2, MODE_CLS = 3;
+// HBM workspace of the two-kernel form.  MODE_CLS: the CLS rows' attention output, bf16 [B][256], then their residual rows, f32
+// [B][256] (a prefix of the workspace).  MODE_HEAD, per board: K and V of the last layer as [head][key][lane half][16] bf16 (the 16
+// values a lane half holds for one (token, head) are contiguous), then the CLS residual row (256 f32).  The size callers allocate is
+// MODE_HEAD's for both.
 constexpr int64_t KV_ELEMS = (int64_t)NH * SEQ * HD;  // per board, per K or V
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -292,6 +300,14 @@ constexpr int L_K = 7 * TILE;             // K   [128 keys][32 d]   bf16, 64-byt
 constexpr int L_VT = 7 * TILE + TILE / 2; // V^T [32 d][128 keys]   bf16, 256-byte rows, chunks swizzled (CPR 16)
 constexpr int L_W1 = 0;                   // [2][2 TILE]: [64][256] slice of linear1.weight of chunk (c & 1)
 constexpr int L_W2 = 4 * TILE;            // [2][2 TILE]: [256][64] slice of linear2.weight of chunk (c & 1)
+// MODE_CLS, last-layer phase: the in_proj ring stays where it is; the out-proj slice and the K / V^T tiles are free and hold the
+// CLS row's staging instead.
+constexpr int L_CX = 6 * TILE;            // normalised CLS columns as one B operand: [16 k-steps][2 halves][8 slots][16 B]
+constexpr int L_CQ = L_CX + 4096;         // Q of the CLS rows, bf16: [2 (head & 1)][8 boards][2 halves][16]
+constexpr int L_CS = L_CQ + 1024;         // scores, f32: [2][8 boards][20] (17 keys, padded to 16-byte rows)
+constexpr int L_CO = L_CS + 1280;         // attention output of the CLS rows, bf16: [8 boards (7: dummy)][8 heads][32]
+constexpr int L_CV = 7 * TILE;            // V, bf16: [2][128 tokens][32], a token's values in the order its two lanes hold them
+static_assert(L_CO + (NBOARD + 1) * D * 2 <= L_CV && L_CV + 2 * NTOK * HD * 2 <= 8 * TILE, "CLS staging fits the free tiles");
 struct LdsMain {
     char w[8 * TILE];
     float bq[D], bo[D], b1[FF], b2[D];
@@ -362,7 +378,7 @@ k_encoder_main(const uint8_t *__restrict__ boards, const float *__restrict__ tab
             }
     }
 
-    const int full_layers = MODE == MODE_HEAD ? n_layers - 1 : n_layers;
+    const int full_layers = (MODE == MODE_HEAD || MODE == MODE_CLS) ? n_layers - 1 : n_layers;
     char *const lds = L.w;
     // The weight blob as a buffer resource; tile addresses below are byte offsets into it (< 2^31: 1.5 MB per layer).
     // Fetches past its end (the "next layer" prefetch of the last layer) are dropped by the hardware's range check.
@@ -782,6 +798,164 @@ k_encoder_main(const uint8_t *__restrict__ boards, const float *__restrict__ tab
         return;
     }
 
+    if constexpr (MODE == MODE_CLS) {
+        // ---- last layer, CLS row only: LayerNorm, K^T / V^T of every head as above, and the attention of each board's CLS query
+        // over its 17 keys while K and V are still on chip.  To HBM go the CLS residual row and the CLS row's attention output
+        // (256 bf16 per board, head dims in KPERM order: what k_encoder_tail's out-proj slices take as their operand).
+        // Every value is formed by the operations, in the order, of the K/V-parking form's tail kernel (k_encoder_tail<true>):
+        // the two forms give the same bits.
+        // Three heads are in flight per iteration it, one stage each between two barriers:
+        //   head it    K^T / V^T chains on every wave (this lane's token: kst / vst); wave it & 3 also runs Q^T of the 7 CLS columns
+        //              (one shared B operand, L_CX; an MFMA output column depends on its own B column only) -> L_CQ
+        //   head it-1  score: each lane's half dot product of its token's K with its board's query, summed across the lane pair
+        //              -> L_CS; its V values -> L_CV
+        //   head it-2  softmax and P.V: thread (board 2w + h, position r) walks the 17 keys in ascending order -> L_CO
+        // The score and softmax instructions are dealt out over the steps of the K/V chain (the vector ALU in the matrix pipe's shadow).
+        const unsigned lwl = (unsigned)(n_layers - 1) * (unsigned)(W_LAYER * 2);
+        const float bq_stage = pblob[(size_t)(n_layers - 1) * P_LAYER + PO_BQKV + tid];
+        __bf16 *const ws_o = ws_k;
+        if (tok_valid && tc == 0) {
+            float *dst = ws_r + (board0 + tb) * D;
+            for (int j = 0; j < 8; ++j)
+                for (int g = 0; g < 4; ++g) {
+                    f32x4 v;
+                    for (int q = 0; q < 4; ++q) v[q] = R[j][4 * g + q];
+                    *reinterpret_cast<f32x4 *>(dst + 32 * j + 8 * g + 4 * h) = v;
+                }
+        }
+        layer_norm(R, xn);
+        L.bq[tid] = bq_stage;
+        if (tb < NBOARD && tc == 0)  // the CLS lanes hold the rows the query is projected from
+            for (int ks = 0; ks < 16; ++ks) *reinterpret_cast<bf16x8 *>(lds + L_CX + ((2 * ks + h) * 8 + tb) * 16) = xn[ks];
+        dma_wait_all();
+        __syncthreads();
+        const int sb = 2 * w + h;                     // softmax stage: this thread's board (7: none) and position r in the head
+        const int sbc = sb < NBOARD ? sb : 0;         // (reads stay inside the stage)
+        bf16x8 kst[2], vst[2];                        // this token's K^T / V^T of the head before
+        constexpr std::true_type yes{};
+        constexpr std::false_type no{};
+        auto cls_head = [&](int it, auto kv_tag, auto fetch_tag, auto score_tag, auto soft_tag) __attribute__((always_inline)) {
+            constexpr bool KV = decltype(kv_tag)::value, FETCH = decltype(fetch_tag)::value;
+            constexpr bool SCORE = decltype(score_tag)::value, SOFT = decltype(soft_tag)::value;
+            const int pb = (it - 1) & 1, sbuf = it & 1;  // stage buffers of head it-1 and of head it-2
+            bf16x8 q0, q1;
+            float d = 0.f, scv[SEQ], m = -3.0e38f, sum = 0.f, o = 0.f;
+            __bf16 vv[SEQ];
+            if constexpr (SCORE) {
+                q0 = *reinterpret_cast<const bf16x8 *>(lds + L_CQ + pb * 512 + tb * 64 + h * 32);
+                q1 = *reinterpret_cast<const bf16x8 *>(lds + L_CQ + pb * 512 + tb * 64 + h * 32 + 16);
+            }
+            if constexpr (SOFT) {
+                const char *src = lds + L_CS + (sbuf * 160 + sbc * 20) * 4;
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 v = *reinterpret_cast<const f32x4 *>(src + 16 * g);
+                    for (int q = 0; q < 4; ++q) scv[4 * g + q] = v[q];
+                }
+                scv[16] = *reinterpret_cast<const float *>(src + 64);
+            }
+            // piece i = 0..31 of the two vector stages
+            auto piece = [&](auto ic) __attribute__((always_inline)) {
+                constexpr int i = decltype(ic)::value;
+                if constexpr (SCORE) {
+                    if constexpr (i == 0) {
+                        for (int s = 0; s < 2; ++s)
+                            *reinterpret_cast<bf16x8 *>(lds + L_CV + pb * (NTOK * HD * 2) + tok * (HD * 2) + (16 * s + 8 * h) * 2) = vst[s];
+                    }
+                    if constexpr (i < 8) {
+                        d += (float)q0[i] * (float)kst[0][i] + (float)q1[i] * (float)kst[1][i];
+                    } else if constexpr (i == 8) {
+                        d = xhalf_sum(d);
+                        *reinterpret_cast<float *>(lds + L_CS + (pb * 160 + tb * 20 + tc) * 4) = d * 0.17677669529663687f;
+                    }
+                }
+                if constexpr (SOFT) {
+                    if constexpr (i < SEQ)
+                        vv[i] = *reinterpret_cast<const __bf16 *>(lds + L_CV + sbuf * (NTOK * HD * 2) + (SEQ * sbc + i) * (HD * 2) + r * 2);
+                    if constexpr (i == 9) {
+                        for (int key = 0; key < SEQ; ++key) m = fmaxf(m, scv[key]);
+                    } else if constexpr (i >= 10 && i < 10 + SEQ) {
+                        constexpr int key = i - 10;
+                        scv[key] = __expf(scv[key] - m);
+                        sum += scv[key];
+                        const float p = (float)(__bf16)scv[key];  // bf16 probabilities (unnormalised), as the MFMA operand would be
+                        o += p * (float)vv[key];
+                    } else if constexpr (i == 10 + SEQ) {
+                        const float inv = 1.0f / sum;
+                        // (unconditional, row 7 is a dummy: under a branch the compiler sinks the whole stage out of the chain into it)
+                        *reinterpret_cast<__bf16 *>(lds + L_CO + sb * (D * 2) + ((it - 2) * HD + r) * 2) = (__bf16)(o * inv);
+                    }
+                }
+            };
+            if constexpr (KV) {
+                // QW (the wave whose turn it is, it & 3): Q^T [32 d][7 CLS columns] of head it in front of the K/V chains, one chain of
+                // 48 steps: the k-step order and the bias start of the tail kernel's product
+                auto chain = [&](auto qw_tag) __attribute__((always_inline)) {
+                    constexpr bool QW = decltype(qw_tag)::value;
+                    constexpr int NQ = QW ? 16 : 0, NS = NQ + 32;
+                    const char *t = wqkv(it);
+                    const char *xsrc = lds + L_CX + (h * 8 + (r & 7)) * 16;  // + 256 per k-step
+                    f32x16 ka2 = {0}, va2 = {0}, qa = {0};
+                    if constexpr (QW) qa = bias_tile(L.bq + HD * it, h);
+                    bf16x8 a[PD], bx[PD];
+                    auto rd = [&](auto sc) __attribute__((always_inline)) {  // operands of step s
+                        constexpr int s = decltype(sc)::value;
+                        if constexpr (s < NQ) {
+                            a[s % PD] = load_w<32>(t, lo, 0, s);
+                            bx[s % PD] = *reinterpret_cast<const bf16x8 *>(xsrc + s * 256);
+                        } else {
+                            a[s % PD] = load_w<32>(t + (1 + (s - NQ) / 16) * TILE, lo, 0, (s - NQ) % 16);
+                        }
+                    };
+                    static_for<0, PD>(rd);
+                    sched_fence();
+                    static_for<0, NS>([&](auto ic) __attribute__((always_inline)) {
+                        constexpr int i = decltype(ic)::value, j = i - NQ;
+                        if constexpr (i < NQ) qa = mfma(a[i % PD], bx[i % PD], qa);
+                        else if constexpr (j < 16) ka2 = mfma(a[i % PD], xn[j], ka2);
+                        else va2 = mfma(a[i % PD], xn[j - 16], va2);
+                        if constexpr (i + PD < NS) rd(std::integral_constant<int, i + PD>{});
+                        if constexpr (FETCH && i % 2 == 0 && i < 24) dma_qkv1(lwl, it + 1, i / 2);  // q, k and v tiles of head it+1
+                        if constexpr (i < 32) piece(ic);
+                        if constexpr (j >= 20 && j < 22)
+                            for (int e = 0; e < 8; ++e) kst[j - 20][e] = (__bf16)ka2[8 * (j - 20) + e];
+                        sched_fence();
+                    });
+                    frag_from_acc(va2, vst);
+                    if constexpr (QW) {
+                        if (r < NBOARD)  // rounded to bf16 like the operand of the full layers' K Q^T product
+                            for (int s = 0; s < 2; ++s) {
+                                bf16x8 qv;
+                                for (int e = 0; e < 8; ++e) qv[e] = (__bf16)qa[8 * s + e];
+                                *reinterpret_cast<bf16x8 *>(lds + L_CQ + (it & 1) * 512 + r * 64 + h * 32 + 16 * s) = qv;
+                            }
+                    }
+                };
+                if (w == (it & 3)) chain(yes);
+                else chain(no);
+            } else {
+                static_for<0, 32>(piece);
+            }
+            dma_wait_all();
+            __syncthreads();  // head it's tiles are free, head it+1's have landed; the stages' outputs are visible
+        };
+        cls_head(0, yes, no, no, no);
+        cls_head(1, yes, yes, yes, no);
+#pragma nounroll
+        for (int it = 2; it < NH - 1; ++it) cls_head(it, yes, yes, yes, yes);
+        cls_head(NH - 1, yes, no, yes, yes);
+        cls_head(NH, no, no, yes, yes);
+        cls_head(NH + 1, no, no, no, yes);
+        // 512-byte rows out, 16 bytes per thread
+        if (tid < NBOARD * 32 && board0 + (tid >> 5) < B)
+            *reinterpret_cast<bf16x8 *>(ws_o + (board0 + (tid >> 5)) * D + (tid & 31) * 8) =
+                *reinterpret_cast<const bf16x8 *>(lds + L_CO + (tid >> 5) * (D * 2) + (tid & 31) * 16);
+        STAMP(18);
+#ifdef G2048_STAMPS
+        stamps.flush(lane, w);
+#endif
+        return;
+    }
+
     if constexpr (MODE == MODE_MEAN) {
         // ---- mean of the 16 board tokens (reference transformer_encoder.py:188-190, encoder_output[:, 1:, :].mean(dim=1)).
         // The last layer's "next layer" prefetches are range-checked but may still land in LDS: drain them before the
@@ -835,7 +1009,11 @@ struct LdsTail {
     float bias[FF];
 };
 static_assert(sizeof(LdsTail) <= 160 * 1024, "LDS budget");
+static_assert(offsetof(LdsTail, w2b) == 6 * TILE, "w and w2b are one 8-tile area (the whole out_proj.weight)");
 
+// KVWS = false: the attention output of the CLS rows comes from k_encoder_main<MODE_CLS> (ws_k = that [B][256] bf16 array, ws_v
+// unused) and the attention block is the out-proj alone.  KVWS = true: Q projection and attention over the parked K / V (A/B arm).
+template <bool KVWS>
 __global__ void __launch_bounds__(THREADS, 1)
 k_encoder_tail(const __bf16 *__restrict__ wblob, const float *__restrict__ pblob, int n_layers, float *__restrict__ features,
                int64_t B, const __bf16 *__restrict__ ws_k, const __bf16 *__restrict__ ws_v, const float *__restrict__ ws_r) {
@@ -868,10 +1046,26 @@ k_encoder_tail(const __bf16 *__restrict__ wblob, const float *__restrict__ pblob
     auto dma_wo = [&](int hd) { dma_tile<4>(wo_of(hd), blob, lw + 2u * (unsigned)(WO_O + HD * hd), D, D, lo, w); };
 
     // ================= attention block =================
+    bf16x8 xn[16];
+    if constexpr (!KVWS) {
+        // out_proj.weight whole, as its eight [256][32] head slices; this board's O row straight into operand fragments (head dims
+        // in KPERM order, as the main kernel wrote them).  R[j] accumulates head 0..7, k-step 0..1: the order of the loop below.
+        for (int hd = 0; hd < NH; ++hd) dma_tile<4>(L.w + hd * TILE, blob, lw + 2u * (unsigned)(WO_O + HD * hd), D, D, lo, w);
+        bf16x8 of[NH][2];
+        for (int hd = 0; hd < NH; ++hd)
+            for (int ks = 0; ks < 2; ++ks) of[hd][ks] = *reinterpret_cast<const bf16x8 *>(ws_k + my_board * D + hd * HD + 16 * ks + 8 * h);
+        dma_wait_all();
+        __syncthreads();
+#pragma unroll
+        for (int hd = 0; hd < NH; ++hd)
+            for (int j = 0; j < 8; ++j) R[j] = gemm_tile<4, 2>(L.w + hd * TILE, lo, j, of[hd], R[j]);
+        pipe_mfma<16 * NH>();
+        __syncthreads();  // every wave is done with the out-proj tiles: the feed-forward tiles go over them
+    }
+    if constexpr (KVWS) {
     dma_q(0);
     dma_wo(0);
     stage_f32(L.bias, P + PO_BQKV, D, tid);
-    bf16x8 xn[16];
     layer_norm(R, xn);
     dma_wait_all();
     __syncthreads();
@@ -930,6 +1124,7 @@ k_encoder_tail(const __bf16 *__restrict__ wblob, const float *__restrict__ pblob
         pipe_mfma<16>();
         dma_wait_all();
         __syncthreads();  // next head's tiles landed; O of this head is free
+    }
     }
 
     // ================= feed-forward block =================
@@ -1002,23 +1197,38 @@ extern "C" int g2048_policy_encoder(const uint8_t *boards, const float *embed_ta
         return G2048_EINVAL;
     if (!aligned16(weights_bf16, params_f32, embed_table, cls_token, features, workspace)) return G2048_EINVAL;
     // the dynamic-LDS limit is a per-device function attribute: set on every call (no latch, no global state)
-    const void *main_fn = workspace ? reinterpret_cast<const void *>(k_encoder_main<MODE_HEAD>)
-                                    : reinterpret_cast<const void *>(k_encoder_main<MODE_FULL>);
+    // G2048_ENCODER_KV_WS=1: the K/V-parking two-kernel form, the A/B arm of the measurement in DESIGN section 3 (read per call: the
+    // library keeps no latched state)
+    const char *e = getenv("G2048_ENCODER_KV_WS");
+    const bool kv_ws = e && e[0] == '1';
+    const void *main_fn = !workspace ? reinterpret_cast<const void *>(k_encoder_main<MODE_FULL>)
+                          : kv_ws    ? reinterpret_cast<const void *>(k_encoder_main<MODE_HEAD>)
+                                     : reinterpret_cast<const void *>(k_encoder_main<MODE_CLS>);
+    const void *tail_fn = kv_ws ? reinterpret_cast<const void *>(k_encoder_tail<true>) : reinterpret_cast<const void *>(k_encoder_tail<false>);
     if (const int rc = allow_dynamic_lds(main_fn, (int)sizeof(LdsMain))) return rc;
     if (workspace)
-        if (const int rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_encoder_tail), (int)sizeof(LdsTail))) return rc;
+        if (const int rc = allow_dynamic_lds(tail_fn, (int)sizeof(LdsTail))) return rc;
     const __bf16 *wb = reinterpret_cast<const __bf16 *>(weights_bf16);
     const unsigned blocks = (unsigned)((B + NBOARD - 1) / NBOARD);
     if (!workspace) {
         hipLaunchKernelGGL(k_encoder_main<MODE_FULL>, dim3(blocks), dim3(THREADS), sizeof(LdsMain), (hipStream_t)stream, boards,
                            embed_table, cls_token, wb, params_f32, n_layers, features, B, (__bf16 *)nullptr, (__bf16 *)nullptr,
                            (float *)nullptr);
+    } else if (!kv_ws) {
+        // workspace prefix: the CLS rows' attention output bf16 [B][256], then their residual rows f32 [B][256]
+        __bf16 *ws_o = reinterpret_cast<__bf16 *>(workspace);
+        float *ws_r = reinterpret_cast<float *>(ws_o + B * D);
+        hipLaunchKernelGGL(k_encoder_main<MODE_CLS>, dim3(blocks), dim3(THREADS), sizeof(LdsMain), (hipStream_t)stream, boards,
+                           embed_table, cls_token, wb, params_f32, n_layers, features, B, ws_o, (__bf16 *)nullptr, ws_r);
+        hipLaunchKernelGGL(k_encoder_tail<false>, dim3((unsigned)((B + NTOK - 1) / NTOK)), dim3(THREADS), sizeof(LdsTail),
+                           (hipStream_t)stream, wb, params_f32, n_layers, features, B, (const __bf16 *)ws_o, (const __bf16 *)nullptr,
+                           (const float *)ws_r);
     } else {
         __bf16 *ws_k = reinterpret_cast<__bf16 *>(workspace), *ws_v = ws_k + B * KV_ELEMS;
         float *ws_r = reinterpret_cast<float *>(ws_v + B * KV_ELEMS);
         hipLaunchKernelGGL(k_encoder_main<MODE_HEAD>, dim3(blocks), dim3(THREADS), sizeof(LdsMain), (hipStream_t)stream, boards,
                            embed_table, cls_token, wb, params_f32, n_layers, features, B, ws_k, ws_v, ws_r);
-        hipLaunchKernelGGL(k_encoder_tail, dim3((unsigned)((B + NTOK - 1) / NTOK)), dim3(THREADS), sizeof(LdsTail),
+        hipLaunchKernelGGL(k_encoder_tail<true>, dim3((unsigned)((B + NTOK - 1) / NTOK)), dim3(THREADS), sizeof(LdsTail),
                            (hipStream_t)stream, wb, params_f32, n_layers, features, B, ws_k, ws_v, ws_r);
     }
     return launch_status();

@@ -177,9 +177,13 @@ int g2048_compact(const uint8_t *tr_boards, const uint8_t *tr_meta, const float 
  *                            b1'[1024] | linear2.bias[256]   (the slots of the folded LayerNorm affines are unused)
  *
  * workspace: NULL = one kernel carries every token through every layer.  Otherwise
- * g2048_policy_encoder_workspace_bytes(B) bytes (16-byte aligned): the last layer is split - a first kernel parks that
- * layer's K/V and the CLS residual row there, a second one batches the CLS tokens of 128 boards per workgroup through the
- * rest of it (only the CLS row of the last layer is read by the "cls" reduction).  Same result up to summation order. */
+ * g2048_policy_encoder_workspace_bytes(B) bytes (16-byte aligned): the last layer is split - a first kernel runs it up to
+ * the CLS row's attention, a second one batches the CLS tokens of 128 boards per workgroup through the rest of it (only
+ * the CLS row of the last layer is read by the "cls" reduction).  Same result up to summation order.
+ * Workspace layout: the first B * 1536 bytes are used - bf16 [B][256] attention output of the CLS rows (per head the 32
+ * dims in the packed weights' column order), then f32 [B][256] their residual rows; the rest is not touched.  With
+ * G2048_ENCODER_KV_WS=1 in the environment (read per call; the A/B arm of the same computation, bit-identical features)
+ * the whole workspace is used: bf16 [B][8 heads][17 keys][2][16] K, the same for V, then the f32 residual rows. */
 int64_t g2048_policy_encoder_workspace_bytes(int64_t B);
 int g2048_policy_encoder(const uint8_t *boards, const float *embed_table, const float *cls_token,
                          const void *weights_bf16, const float *params_f32, int n_layers, float *features,

@@ -11,7 +11,7 @@ for p in p1 p2; do cp /tmp/pe/$p/*/*_counter_collection.csv gpurun_out/enc/$p.cs
 python3 - <<'PY'
 import csv, collections, json
 out = {}
-for pats, tag in ((("mainILi1E", "k_encoder_main<1>"), "head"), (("k_encoder_tail",), "tail"), (("mainILi0E", "k_encoder_main<0>"), "single")):
+for pats, tag in ((("mainILi3E", "k_encoder_main<3>"), "cls"), (("mainILi1E", "k_encoder_main<1>"), "head"), (("k_encoder_tail",), "tail"), (("mainILi0E", "k_encoder_main<0>"), "single")):
     d = {}
     for p in ("p1", "p2"):
         agg = collections.defaultdict(list)
