@@ -8,6 +8,7 @@ every chunk one byte per env is read back (the largest tile on a training board)
 the lock-step count at the end of the first chunk after which a training board holds a 2048 tile.  Evaluation = the histogram
 protocol of ``evaluate_max_tile`` (``--eval-episodes`` episodes, seed 42, batches of 100, largest tile of the final board), at
 ``--evals`` points spread evenly over the budget, the last one at its end; evaluation time is excluded from the training clock.
+``--eval-plies 0 1 2`` plays every evaluation point once per listed expectimax depth over the network (0: greedy, the default).
 """
 import argparse
 import json
@@ -32,6 +33,8 @@ def main():
     ap.add_argument("--evals", type=int, default=3, help="evaluation points, evenly spread, the last at the end of the budget")
     ap.add_argument("--eval-at", type=float, nargs="*", default=None, help="evaluation points in minutes instead of --evals")
     ap.add_argument("--eval-episodes", type=int, default=1000)
+    ap.add_argument("--eval-plies", type=int, nargs="+", default=[0], choices=(0, 1, 2),
+                    help="expectimax depths to evaluate at: every evaluation point plays the same seeds once per depth")
     ap.add_argument("--chunk", type=int, default=50, help="lock-steps between two looks at the clock")
     ap.add_argument("--seed", type=int, default=0, help="seed of the training environments")
     ap.add_argument("--out", default=None, help="write the JSON result here")
@@ -59,12 +62,13 @@ def main():
             print(f"first 2048 tile on a training board after {trained:.1f} s, {trainer.lock_steps} lock-steps", flush=True)
         if trained >= points[0]:
             points.pop(0)
-            ev = evaluate_ntuple(net, dev, num_episodes=args.eval_episodes, seed=42)
-            ev.update(train_seconds=round(trained, 2), lock_steps=trainer.lock_steps, episodes_trained=episodes,
-                      max_abs_weight=int(net.weights.abs().max().item()))
-            result["evaluations"].append(ev)
-            print(f"{trained / 60:.2f} min, {trainer.lock_steps} lock-steps: mean max tile {ev['mean_max_tile']:.1f}, "
-                  f"percent {ev['percent']}", flush=True)
+            for plies in args.eval_plies:
+                ev = evaluate_ntuple(net, dev, num_episodes=args.eval_episodes, seed=42, plies=plies)
+                ev.update(plies=plies, train_seconds=round(trained, 2), lock_steps=trainer.lock_steps, episodes_trained=episodes,
+                          max_abs_weight=int(net.weights.abs().max().item()))
+                result["evaluations"].append(ev)
+                print(f"{trained / 60:.2f} min, {trainer.lock_steps} lock-steps, plies {plies}: mean max tile "
+                      f"{ev['mean_max_tile']:.1f}, percent {ev['percent']}", flush=True)
     result["lock_steps"] = trainer.lock_steps
     result["lock_steps_per_s"] = round(trainer.lock_steps / trained, 1)
     result["env_steps_per_s"] = round(trainer.lock_steps * args.envs / trained, 1)

@@ -477,6 +477,27 @@ def ntuple_scores(boards, weights, tuple_cells, frac_bits: int, scores, values):
            "g2048_ntuple_scores")
 
 
+def ntuple_expectimax_workspace_floats(B: int, plies: int) -> int:
+    """The f32 elements of ``workspace`` that ``ntuple_expectimax`` needs: 0 for one ply, 128 B for two."""
+    n = load().g2048_ntuple_expectimax_workspace_floats(int(B), int(plies))
+    if n < 0:
+        raise NativeError(f"ntuple_expectimax: no workspace size for B={B}, plies={plies} (plies is 1 or 2, B at most 2^24 / 2^20)")
+    return n
+
+
+def ntuple_expectimax(boards, weights, tuple_cells, frac_bits: int, plies: int, gamma: float, workspace, scores, values):
+    """scores f32 [B,4] = the ``plies``-ply (1 or 2) expectimax Q over the n-tuple network's greedy value, values f32 [B] = the max
+    over the legal moves.  workspace: f32 [>= 128 B] for two plies, None (or anything) for one; its contents do not matter."""
+    cells, m, L = _tuple_cells(tuple_cells)
+    B, plies = values.numel(), int(plies)
+    need = ntuple_expectimax_workspace_floats(B, plies)
+    _check(load().g2048_ntuple_expectimax(_dev(boards, u8, 16 * B, "boards"), B, _dev(weights, i32, m * 16 ** L, "weights"),
+                                          cells.ctypes.data, m, L, int(frac_bits), plies, float(gamma),
+                                          _dev(workspace, f32, need, "workspace", optional=need == 0),
+                                          _dev(scores, f32, 4 * B, "scores"), _dev(values, f32, B, "values"), _stream()),
+           "g2048_ntuple_expectimax")
+
+
 def ntuple_td_accumulate(prev_after, flag, target, weights, tuple_cells, frac_bits: int, alpha: float, acc, cnt, td_error=None):
     """The accumulate half of one TD(0) lock-step: acc i64 [m, 16^L] += delta, cnt i32 [m, 16^L] += 1 at the entries of every env
     with flag != 0.  td_error f32 [B] or None."""

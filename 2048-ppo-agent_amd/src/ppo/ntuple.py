@@ -23,6 +23,20 @@ from .q_player import QPlayer
 
 DEFAULT_TUPLES = ((0, 1, 2, 3, 4, 5), (4, 5, 6, 7, 8, 9), (0, 1, 2, 4, 5, 6), (4, 5, 6, 8, 9, 10))
 MAX_TUPLES, MAX_CELLS, MAX_FRAC_BITS = 8, 6, 20
+SEARCH_CHUNK = 1 << 16  # roots per two-ply call: 128 workspace floats each
+
+
+def _check_search(plies, gamma):
+    """-> (plies, gamma) as (int, float); ``ValueError`` for plies outside {0, 1, 2} or a gamma that is negative or not finite."""
+    if isinstance(plies, bool) or plies not in (0, 1, 2):
+        raise ValueError(f"plies must be 0, 1 or 2, got {plies!r}")
+    try:
+        g = float(gamma)
+    except (TypeError, ValueError):
+        raise ValueError(f"gamma must be a finite non-negative number, got {gamma!r}") from None
+    if not (np.isfinite(g) and g >= 0.0):
+        raise ValueError(f"gamma must be a finite non-negative number, got {gamma!r}")
+    return int(plies), g
 
 
 def _check_tuples(tuples) -> np.ndarray:
@@ -63,6 +77,7 @@ class NTupleNetwork:
         self.m, self.L = self.cells.shape
         self.device = _device(device)
         self.weights = torch.zeros((self.m, 16 ** self.L), dtype=torch.int32, device=self.device)
+        self._search_ws = None  # the two-ply workspace, allocated at the first two-ply call
 
     def values(self, boards: torch.Tensor) -> torch.Tensor:
         """boards u8 [n, 16] -> V f32 [n]."""
@@ -81,6 +96,28 @@ class NTupleNetwork:
         v = torch.empty(B, dtype=torch.float32, device=boards.device)
         if B:
             nv.ntuple_scores(boards, self.weights, self.cells, self.frac_bits, q, v)
+        return q, v
+
+    def expectimax(self, boards: torch.Tensor, plies: int, gamma: float = 1.0):
+        """boards u8 [B, 16] -> (q f32 [B, 4], v f32 [B]) of ``plies``-ply expectimax whose leaf is ``scores``' v (the network's
+        greedy value), searched inside the kernel (``g2048_ntuple_expectimax``): one launch for one ply, two for two, nothing
+        read back.  ``plies=0`` is ``scores``.  Two plies go in chunks of at most 2^16 roots through one cached 32 MB workspace."""
+        plies, gamma = _check_search(plies, gamma)
+        if plies == 0:
+            return self.scores(boards)
+        boards = boards.contiguous()
+        B = boards.shape[0]
+        q = torch.empty((B, 4), dtype=torch.float32, device=boards.device)
+        v = torch.empty(B, dtype=torch.float32, device=boards.device)
+        ws = None
+        if plies == 2 and B:
+            ws = self._search_ws
+            if ws is None or ws.device != boards.device:
+                ws = self._search_ws = torch.empty(SEARCH_CHUNK * 128, dtype=torch.float32, device=boards.device)
+        step = SEARCH_CHUNK if plies == 2 else 1 << 24  # the entry point's own limit for one ply
+        for s in range(0, B, step):
+            e = min(B, s + step)
+            nv.ntuple_expectimax(boards[s:e], self.weights, self.cells, self.frac_bits, plies, gamma, ws, q[s:e], v[s:e])
         return q, v
 
     def save(self, path: str) -> None:
@@ -104,13 +141,17 @@ class NTupleActionFunction(QPlayer):
     its key stream and the trajectory format are untouched.  The recorded ``log_prob`` is the log-softmax of scores at the chosen action:
     NOT a policy probability (``q`` is in score units), so such trajectories are for evaluation only, not for a PPO update.
     ``rng_mode``: anything ``resolve_rng_mode`` takes; an unknown spelling raises ``ValueError`` (it used to mean "partitionable").
+    ``plies`` (0, 1 or 2) puts that many plies of expectimax over every spawn in front of the greedy value
+    (``NTupleNetwork.expectimax``; 0, the default, is ``scores`` itself), discounted by ``gamma`` per ply (1.0: the TD(0) learner is
+    undiscounted); anything else raises ``ValueError`` before a device is touched.
     """
 
     compact = True
 
-    def __init__(self, network: NTupleNetwork, device=None, rng_mode=None):
+    def __init__(self, network: NTupleNetwork, device=None, rng_mode=None, *, plies: int = 0, gamma: float = 1.0):
         if not isinstance(network, NTupleNetwork):
             raise ValueError(f"network must be an NTupleNetwork, got {type(network).__name__}")
+        self.plies, self.gamma = _check_search(plies, gamma)
         self.network = network
         self.device = device
         self.rng_mode = rng_mode
@@ -118,7 +159,7 @@ class NTupleActionFunction(QPlayer):
     @torch.no_grad()
     def policy_fn(self, boards: torch.Tensor, masks: torch.Tensor = None):
         """boards u8 [B, 16], masks unused (legality is ``afterstate != board``) -> (q f32 [B, 4], v f32 [B])."""
-        return self.network.scores(boards)
+        return self.network.expectimax(boards, self.plies, self.gamma)
 
     policy_fn.needs_masks = False
 

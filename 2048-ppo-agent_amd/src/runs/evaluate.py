@@ -91,10 +91,11 @@ def evaluate_monte_carlo(device, num_episodes: int = 1000, seed: int = 42, agent
             agent.train(was_training)
 
 
-def evaluate_ntuple(network, device, num_episodes: int = 1000, seed: int = 42, rng_mode=None) -> Dict:
+def evaluate_ntuple(network, device, num_episodes: int = 1000, seed: int = 42, rng_mode=None, plies: int = 0, gamma: float = 1.0) -> Dict:
     """The same protocol (same seeds, same env and key stream) played by ``NTupleActionFunction(network)``: the legal move with the
-    best ``reward + V(afterstate)`` under the n-tuple network, no other network or search involved."""
+    best ``reward + V(afterstate)`` under the n-tuple network, no other network involved; ``plies`` (1 or 2) searches that many
+    plies of expectimax over that value first."""
     from ..ppo.ntuple import NTupleActionFunction
 
-    fn = NTupleActionFunction(network, device=device, rng_mode=rng_mode)
+    fn = NTupleActionFunction(network, device=device, rng_mode=rng_mode, plies=plies, gamma=gamma)
     return evaluate_max_tile(fn, num_episodes, seed, rng_mode=rng_mode, device=device)

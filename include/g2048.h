@@ -441,6 +441,34 @@ int g2048_ntuple_td_apply(const uint8_t *prev_after, const uint8_t *flag, int64_
 int g2048_ntuple_link(const uint8_t *tr_boards_row, const uint8_t *tr_meta_row, int64_t B, uint8_t *prev_after, uint8_t *flag,
                       void *stream);
 
+/* ---- n-tuple expectimax (one or two plies of search over the n-tuple network, inside the kernel) ----
+ * All f32, every operation individually rounded, table sums integer as above; order and rounding as g2048_lookahead_reduce.
+ *   Q0(s,a), V0(s) = scores and values of g2048_ntuple_scores
+ *   for k = 1, 2:
+ *     acc      = sum over the empty cells c of after_a(s), ascending cell index, starting from +0, of
+ *                0.9f * V_{k-1}(after_a + tile 2 at c) + 0.1f * V_{k-1}(after_a + tile 4 at c)
+ *     Q_k(s,a) = (float)r(s,a) + gamma * (acc / (float)n_empty) where a is legal (correctly rounded division), +0 where not
+ *     V_k(s)   = the max of Q_k(s,a) over the legal a, +0 if there is none (so a child without a legal move is worth +0)
+ * The children of a board have fixed slots, slot = a * 32 + cell * 2 + (tile - 1) (128 of them; a slot exists if a is legal and
+ * the cell is empty in after_a): nothing is enumerated, counted or scanned, no child board reaches memory, nothing is read
+ * back.  One ply is one launch of one workgroup per root; two plies are one workgroup per (root, slot) that writes V1 of the
+ * child to workspace[root * 128 + slot], then one lane per (root, action).  A workspace entry whose slot does not exist is
+ * neither written nor read: the workspace needs no clearing and its contents do not change the result.  No atomics: the bits
+ * do not depend on scheduling. */
+
+/* The f32 elements of workspace that g2048_ntuple_expectimax needs: 0 for plies == 1, 128 B for plies == 2; -1 for plies not 1
+ * or 2, B < 1, B > 2^24 (one ply) or B > 2^20 (two plies). */
+int64_t g2048_ntuple_expectimax_workspace_floats(int64_t B, int plies);
+
+/* scores f32[B][4] = Q_plies(boards[b], a), values f32[B] = V_plies(boards[b]); rows at or past B are not touched.  gamma is
+ * rounded to f32 once.
+ * G2048_EINVAL, before any device work: a null pointer (workspace may be null when plies == 1), B or plies for which
+ * g2048_ntuple_expectimax_workspace_floats returns -1, the network or frac_bits as for g2048_ntuple_values, gamma negative or
+ * not finite, boards not 16-byte aligned, weights, scores or values not 4-byte aligned, workspace not 8-byte aligned. */
+int g2048_ntuple_expectimax(const uint8_t *boards, int64_t B, const int32_t *weights, const uint8_t *tuple_cells /*host*/, int m,
+                            int L, int frac_bits, int plies, double gamma, float *workspace, float *scores, float *values,
+                            void *stream);
+
 /* ---- policy network (update): attention for 17-token sequences ------------------------------------- */
 
 /* softmax(q k^T * scale) v with attention dropout, head_dim 32, Sk = 17 keys, Sq = 17 queries (or 1: the CLS row
