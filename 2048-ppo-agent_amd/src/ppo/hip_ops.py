@@ -5,11 +5,14 @@ Each ``torch.autograd.Function`` here stands in for a group of PyTorch operators
 on the update path = HIP device + gradients wanted + bf16 autocast (``_train_bf16``); everywhere else (CPU, fp32, eval)
 the callers fall back to the plain PyTorch operators.  INTEGRATION.md lists which operator each one replaces.
 """
+import os
 import weakref
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from ..g2048 import native as nv
 
 
 class Bf16Shadow:
@@ -20,18 +23,18 @@ class Bf16Shadow:
 
     _live = weakref.WeakSet()
 
-    def __init__(self, params, transposed=(), packed=(), packed_only=(), packed_t_only=()):
+    def __init__(self, params, transposed=(), packed=(), packed_t=()):
         self.params = list(params)
         self.key, self.flat, self.views = None, None, None
-        self.transposed = tuple(transposed)  # indices of 2-D params that also get a [in, out] copy (``tviews[i]``)
-        self.tviews = {}
-        # indices of 2-D params that also get fragment-packed copies of the tensor and of its transpose (``pviews[i]``,
-        # ``ptviews[i]``: flat bf16 tensors in the MFMA operand order of include/g2048.h, read by the fused CLS tail kernels)
-        self.packed = tuple(packed)
-        # the same, one orientation only: ``packed_only`` the tensor itself (forward operand of g2048_linear_add_ln_fwd),
-        # ``packed_t_only`` its transpose (operand of the fused input-gradient GEMM, g2048_linear_add_ln_bwd)
-        self.packed_only, self.packed_t_only = tuple(packed_only), tuple(packed_t_only)
-        self.pviews, self.ptviews = {}, {}
+        # three independent requests, each a set of indices of 2-D params: ``transposed`` a row-major [in, out] copy (``tviews[i]``),
+        # ``packed`` a fragment-packed copy of the tensor (``pviews[i]``: a flat bf16 tensor in the MFMA operand order of
+        # include/g2048.h; the forward operand of g2048_linear_add_ln_fwd and of the fused CLS tail), ``packed_t`` a fragment-packed
+        # copy of its transpose (``ptviews[i]``: the operand of the input-gradient GEMMs, g2048_linear_add_ln_bwd / g2048_cls_tail_bwd)
+        self.transposed = tuple(transposed)
+        self._want = (tuple(packed), tuple(packed_t))
+        # the indices with BOTH packed copies (what the fused CLS tail reads); empty for a shadow built without packed copies
+        self.packed = tuple(i for i in self._want[0] if i in self._want[1])
+        self.tviews, self.pviews, self.ptviews = {}, {}, {}
         # set by an optimiser that rewrites the shadow together with the parameters (optim.flat_step.FlatAdamWStep): the
         # shadow then copies only when its key is stale (someone else changed a parameter), also during a hipGraph capture
         self.maintainer = None
@@ -40,12 +43,10 @@ class Bf16Shadow:
     def __getstate__(self):
         """copy.deepcopy / pickle of an agent: the copy starts cold - no buffers and no maintainer (both belong to the
         original's optimiser, which must not travel with a pickled module) - and registers itself like a new shadow."""
-        return {"params": self.params, "transposed": self.transposed, "packed": self.packed, "packed_only": self.packed_only,
-                "packed_t_only": self.packed_t_only}
+        return {"params": self.params, "transposed": self.transposed, "packed": self._want[0], "packed_t": self._want[1]}
 
     def __setstate__(self, state):
-        self.__init__(state["params"], state["transposed"], state.get("packed", ()), state.get("packed_only", ()),
-                      state.get("packed_t_only", ()))
+        self.__init__(state["params"], state["transposed"], state.get("packed", ()), state.get("packed_t", ()))
 
     def invalidate(self):
         self.key = None
@@ -84,21 +85,16 @@ class Bf16Shadow:
                 self.views = [self.flat[o:o + q.numel()].view(q.shape) for o, q in zip(offs, ps)]
                 self.tviews = {i: torch.empty(ps[i].shape[::-1], dtype=torch.bfloat16, device=ps[0].device)
                                for i in self.transposed}
-                self.pviews = {i: torch.empty(ps[i].numel(), dtype=torch.bfloat16, device=ps[0].device)
-                               for i in self.packed + self.packed_only}
-                self.ptviews = {i: torch.empty(ps[i].numel(), dtype=torch.bfloat16, device=ps[0].device)
-                                for i in self.packed + self.packed_t_only}
+                self.pviews, self.ptviews = ({i: torch.empty(ps[i].numel(), dtype=torch.bfloat16, device=ps[0].device) for i in want}
+                                             for want in self._want)
             with torch.no_grad():
                 torch._foreach_copy_(self.views, [q.detach() for q in ps])
                 for i, tv in self.tviews.items():
                     tv.copy_(self.views[i].t())
-                if self.pviews or self.ptviews:
-                    from ..g2048 import native as nv
-
-                    for i in self.pviews:
-                        self.pviews[i].copy_(nv.pack_fragments(self.views[i]))
-                    for i in self.ptviews:
-                        self.ptviews[i].copy_(nv.pack_fragments(self.views[i].t()))
+                for i in self.pviews:
+                    self.pviews[i].copy_(nv.pack_fragments(self.views[i]))
+                for i in self.ptviews:
+                    self.ptviews[i].copy_(nv.pack_fragments(self.views[i].t()))
             # a copy recorded into a hipGraph has not run yet: leave the key stale so that the next eager use copies for real
             self.key = None if (ps[0].is_cuda and torch.cuda.is_current_stream_capturing()) else key
         return self.views
@@ -150,8 +146,6 @@ class GradSink:
         tell the owner.  A no-op unless EVERY early parameter has been written (else ``flush`` sums everything at the end)."""
         if self.early_done or not self.early or not self.early <= self.written:
             return
-        from ..g2048 import native as nv
-
         nv.reduce_jobs(self.early_jobs)
         self.early_jobs, self.early_done = [], True
         if self.on_early is not None:
@@ -170,8 +164,6 @@ class GradSink:
             self.add(bias, cs, N, N, slices, b_offset)
 
     def flush(self):
-        from ..g2048 import native as nv
-
         if self.dw_jobs:
             nv.dweight_jobs(self.dw_jobs)
             self.dw_jobs = []
@@ -211,14 +203,22 @@ def _sum_f32(t: torch.Tensor, dim: int = 0) -> torch.Tensor:
     return torch.sum(t, dim, dtype=torch.float32)
 
 
+def _env_on(name: str, default: str = "1") -> bool:
+    """An on/off switch of the environment, read per call: off for 0 / false / no / off (any case)."""
+    return os.environ.get(name, default).strip().lower() not in ("0", "false", "no", "off")
+
+
+def _colsum_ok(t: torch.Tensor, max_width=None) -> bool:
+    """The tensors ``g2048_colsum`` takes ([rows, N] on the device); ``max_width``: the cap of its partial-sums-only form."""
+    N = t.shape[-1]
+    return (t.is_cuda and t.dim() == 2 and t.stride(1) == 1 and N % 4 == 0 and (max_width is None or N <= max_width)
+            and t.stride(0) % 4 == 0 and t.dtype in (torch.bfloat16, torch.float32) and t.data_ptr() % 16 == 0)
+
+
 def _colsum(t: torch.Tensor, out=None) -> torch.Tensor:
     """f32 column sums of a [rows, N] device tensor (bias gradients): ``g2048_colsum`` (fixed summation order and safe
     inside a replayed hipGraph, unlike at::sum's semaphore-based cross-workgroup stage) when the shape allows."""
-    N = t.shape[-1]
-    if t.is_cuda and t.dim() == 2 and t.stride(1) == 1 and N % 4 == 0 and t.stride(0) % 4 == 0 \
-            and t.dtype in (torch.bfloat16, torch.float32) and t.data_ptr() % 16 == 0:
-        from ..g2048 import native as nv
-
+    if _colsum_ok(t):
         return nv.colsum(t, out)
     if t.is_cuda and torch.cuda.is_current_stream_capturing():
         # at::sum's cross-workgroup stage yields wrong values when replayed from a hipGraph on this stack (NOTES.md 3):
@@ -246,11 +246,11 @@ def _hip_linear(x2: torch.Tensor, wb: torch.Tensor, bias_f32=None):
     """x2 @ wb^T (+ bias) through ``g2048_linear_bf16`` for the shapes where its weights-stationary layout beats
     hipBLASLt's pick on this chip (K <= 256 with a wide output: linear1 forward 55 -> 38 us, linear2 input gradient
     48 -> 38 us at 34 816 tokens; tools/probe_linear.py), else None."""
+    # the wide projections of the update (in_proj 256 -> 768, the last layer's K/V 256 -> 512) also go through it instead of hipBLASLt:
+    # 2.73 -> 2.69 ms per minibatch in the pipeline (isolated and cache-warm hipBLASLt is the faster one, tools/probe_linear.py)
     K, N = x2.shape[-1], wb.shape[0]
     if K > 256 or N % 256 or x2.shape[0] < 4096:
         return None
-    from ..g2048 import native as nv
-
     if not nv.linear_ok(x2, wb):
         return None
     return nv.linear_bf16(x2, wb, bias_f32)
@@ -261,16 +261,12 @@ def _stationary_ok(x2: torch.Tensor, wb: torch.Tensor) -> bool:
     K, N = x2.shape[-1], wb.shape[0]
     if K > 256 or N < 512 or N % 256 or x2.shape[0] < 4096:
         return False
-    from ..g2048 import native as nv
-
     return nv.linear_ok(x2, wb)
 
 
 def _rowgemm_on() -> bool:
     """G2048_ROWGEMM=0 switches the fused Linear + add + LayerNorm launches (g2048_linear_add_ln_fwd / _bwd) off: the A/B switch."""
-    import os
-
-    return os.environ.get("G2048_ROWGEMM", "1").strip().lower() not in ("0", "false", "no", "off")
+    return _env_on("G2048_ROWGEMM")
 
 
 class HLink:
@@ -289,8 +285,6 @@ class HLink:
         """Called by the consumer's backward: True if the producer will compute the input gradient itself.  ``tile_stride``: the packed
         weight is K columns of a wider packed matrix (``native.rowgemm_ok``); ``extra`` bf16 [T / extra_period, 256]: added to the
         gradient on the rows t % extra_period == 0 (the CLS rows' share of the last layer's query projection)."""
-        from ..g2048 import native as nv
-
         if (not self.armed or wt_packed is None or self.pending is not None or not _rowgemm_on()
                 or not nv.rowgemm_ok(dy2, wt_packed, tile_stride)):
             return False
@@ -316,19 +310,14 @@ class FFNLink:
         self.bias_param, self.db_sunk = None, False  # linear1's bias; True when a GradSink took its gradient
 
 
-
-# the wide projections of the update (in_proj 256 -> 768, the last layer's K/V 256 -> 512) go through g2048_linear_bf16 instead of
-# hipBLASLt: 2.73 -> 2.69 ms per minibatch in the pipeline (isolated and cache-warm hipBLASLt is the faster one, tools/probe_linear.py)
-_SINK_SLICES = 16  # split-K slices of a weight gradient when a GradSink sums them
+_SPLIT_K = 16  # token slices of a split-K weight gradient, whether at::sum or a GradSink adds them up
 
 
 def _dweight_parts(dy2: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
     """The first stage of ``_dweight``: bf16 [parts, out, in] whose sum over parts is dW (parts = 16 split-K slices for a
     long token axis, else 1)."""
-    T, S = x2.shape[0], _SINK_SLICES
+    T, S = x2.shape[0], _SPLIT_K
     if T >= 16384:  # the minibatch's token axis: g2048_dweight_bf16, [128 x 128] blocks x slices = 128-256 workgroups
-        from ..g2048 import native as nv
-
         slices = 16 if dy2.shape[1] * x2.shape[1] > 256 * 256 else 32
         if nv.dweight_ok(dy2, x2, slices):
             return nv.dweight_parts(dy2, x2, slices, block_rows=128)
@@ -347,8 +336,6 @@ def _deferred_dweight(sink, weight, bias, dy2, x2, w_offset: int = 0, b_offset: 
     # join the launch as well - each was a batched GEMM node of 8-14 us of its own)
     if x2.shape[0] < 2048:
         return False
-    from ..g2048 import native as nv
-
     slices, dtype = _dweight_parts_config()
     if not nv.dweight_ok(dy2, x2, slices):
         return False
@@ -360,8 +347,6 @@ def _dweight_parts_config():
     """(token slices, dtype of the partial products) of the deferred weight gradients.  Default 8 bf16 slices; G2048_DWEIGHT_PARTS =
     bf16x16 / f32x8 are the other two arms of round 4's multi-seed A/B (profiles/round4_dweight_slices_seeds.txt), read per call so a
     sweep can flip it between trainers of one process."""
-    import os
-
     v = os.environ.get("G2048_DWEIGHT_PARTS", "bf16x8").strip().lower()
     table = {"bf16x8": (8, torch.bfloat16), "bf16x16": (16, torch.bfloat16), "f32x8": (8, torch.float32), "f32x16": (16, torch.float32)}
     if v not in table:
@@ -387,18 +372,10 @@ def _sink_weight(sink, param, dy2, x2, dst_offset: int = 0):
     sink.add(param, parts, n, n, parts.shape[0], dst_offset)
 
 
-def _colsum_sinkable(t: torch.Tensor) -> bool:
-    N = t.shape[-1]
-    return (t.is_cuda and t.dim() == 2 and t.stride(1) == 1 and N % 4 == 0 and N <= 1024 and t.stride(0) % 4 == 0
-            and t.dtype in (torch.bfloat16, torch.float32) and t.data_ptr() % 16 == 0)
-
-
 def _sink_bias(sink, param, dy2, dst_offset: int = 0):
     """Bias gradient = column sums of dy2, second stage left to the sink (first stage: g2048_colsum's partial kernel)."""
-    from ..g2048 import native as nv
-
     N = dy2.shape[-1]
-    if _colsum_sinkable(dy2):
+    if _colsum_ok(dy2, max_width=1024):
         ws = nv.colsum_partial(dy2)
         sink.add(param, ws, N, N, ws.shape[0], dst_offset)
     else:  # widths the partial kernel does not take: a finished column sum, copied into place by the sink
@@ -410,7 +387,7 @@ def _dweight(dy2: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
     into a tiny [out, in] matrix; hipBLASLt runs that as 16-64 workgroups on 256 CUs (177 us per GEMM).  Cutting the
     token axis into 16 slices turns it into a batched GEMM with 16x the workgroups plus an f32 sum of the partials:
     42 us, 4x faster, and the f32 sum is at least as accurate as the single bf16-output GEMM it replaces."""
-    T, S = x2.shape[0], _LinearSplitK.SLICES
+    T, S = x2.shape[0], _SPLIT_K
     if T % S == 0 and T // S >= 1024:
         return _sum_f32(_dweight_parts(dy2, x2))  # g2048_dweight_bf16 when it takes the operands, else the batched GEMM
     return (dy2.t() @ x2).float()
@@ -420,8 +397,6 @@ class _LinearSplitK(torch.autograd.Function):
     """``F.linear`` in bf16 (what autocast does) with a split-K weight gradient (``_dweight``), f32 gradients for the f32
     master weight/bias produced directly by the reductions, and optional pre-cast bf16 shadows ``wb``/``bb`` of the
     masters (``Bf16Shadow``) so that no cast kernels run per call."""
-
-    SLICES = 16
 
     @staticmethod
     def forward(ctx, x, weight, bias, wb=None, bb=None, h_link=None, wt_packed=None):
@@ -486,8 +461,6 @@ class _LinearRelu(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from ..g2048 import native as nv
-
         x2, wb, y = ctx.saved_tensors
         weight, bias = ctx.params
         shape, x_dtype = ctx.meta
@@ -516,8 +489,6 @@ class _InProjCls(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, weight, bias, wb, bb, h_link=None, wt_packed=None):
-        from ..g2048 import native as nv
-
         ctx.h_link, ctx.wt_packed = h_link, wt_packed  # (HLink: the producer of h may run the K/V input-gradient GEMM itself)
         B, S, D = h.shape
         h_cls = None
@@ -542,24 +513,17 @@ class _InProjCls(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dq, dkv):
-        from ..g2048 import native as nv
-
         h, wb = ctx.saved_tensors
         B, S, D = h.shape
         dq2, dkv2 = dq.reshape(B, D).contiguous(), dkv.reshape(B * S, 2 * D).contiguous()
         dh = None
         link, wtp = ctx.h_link, ctx.wt_packed
-        if link is not None and wtp is not None and D == 256:
-            # the node that produced h runs dkv . W_kv inside its LayerNorm backward (g2048_linear_add_ln_bwd): W_kv^T = columns
-            # D .. 3 D of the packed in_proj^T [256][3 D] (k-steps D / 16 onwards, tile stride 3 D / 16 fragments), and the CLS rows' share
-            # of the query projection travels as an extra term on every S-th row
-            if link.offer(dkv2, wtp[(D // 16) * 512:], tile_stride=(3 * D // 16) * 512, extra=(dq2 @ wb[:D]).contiguous(), extra_period=S):
-                dh = None
-            else:
-                link = None
-        else:
-            link = None
-        if link is None:
+        # the node that produced h may run dkv . W_kv inside its LayerNorm backward (g2048_linear_add_ln_bwd): W_kv^T = columns
+        # D .. 3 D of the packed in_proj^T [256][3 D] (k-steps D / 16 onwards, tile stride 3 D / 16 fragments), and the CLS rows' share
+        # of the query projection travels as an extra term on every S-th row
+        if not (link is not None and wtp is not None and D == 256
+                and link.offer(dkv2, wtp[(D // 16) * 512:], tile_stride=(3 * D // 16) * 512, extra=(dq2 @ wb[:D]).contiguous(),
+                               extra_period=S)):
             dh = (dkv2 @ wb[D:]).view(B, S, D)
             dh0 = dh[:, 0]  # [B, D] with row stride S * D: the CLS rows receive the query's gradient in the GEMM's epilogue
             torch.addmm(dh0, dq2, wb[:D], out=dh0)
@@ -574,17 +538,12 @@ class _InProjCls(torch.autograd.Function):
             _sink_weight_bias(sink, weight, bias, dq2, h_cls, 0, 0)
             _sink_weight_bias(sink, weight, bias, dkv2, h.view(B * S, D), D * D, D)
             return dh, None, None, None, None, None, None
-
-        def weight_grads():
-            dw = torch.empty((3 * D, D), dtype=torch.float32, device=h.device)
-            dw[:D] = dq2.t() @ h_cls
-            dw[D:] = _dweight(dkv2, h.view(B * S, D))
-            db = torch.empty(3 * D, dtype=torch.float32, device=h.device)
-            _colsum(dq2, db[:D])
-            _colsum(dkv2, db[D:])
-            return dw, db
-
-        dw, db = weight_grads()
+        dw = torch.empty((3 * D, D), dtype=torch.float32, device=h.device)
+        dw[:D] = dq2.t() @ h_cls
+        dw[D:] = _dweight(dkv2, h.view(B * S, D))
+        db = torch.empty(3 * D, dtype=torch.float32, device=h.device)
+        _colsum(dq2, db[:D])
+        _colsum(dkv2, db[D:])
         return dh, dw, db, None, None, None, None
 
 
@@ -617,6 +576,24 @@ def _seed_pair(t: torch.Tensor, p_drop: float):
     return _seed(), 0
 
 
+def _attn_launch(q, kv, nhead, p_drop, seed, lse, o=None, do=None, dq=None, dkv=None):
+    """One launch of ``g2048_attn_fwd`` (writes ``o`` and ``lse``) or, with ``do``, of ``g2048_attn_bwd`` (writes ``dq`` / ``dkv``, laid out
+    like q / kv).  ``q`` None: ``kv`` is the packed in_proj output [B, S, 3 hw] and every row queries (the queries are its first
+    third, ``dkv`` = the packed d(qkv)); else q [B, 1, hw] against kv [B, S, 2 hw].  All operands contiguous bf16."""
+    B, S, W = kv.shape
+    hw, Sq, q_strides = (W // 3, S, (S * W, W)) if q is None else (W // 2, 1, (W // 2, 0))
+
+    def ptrs(q_t, kv_t):  # byte addresses of Q, K, V (bf16: 2 bytes per element)
+        base = kv_t.data_ptr()
+        return (base, base + 2 * hw, base + 4 * hw) if q_t is None else (q_t.data_ptr(), base, base + 2 * hw)
+
+    tail = (B, nhead, Sq, q_strides + (S * W, W) * 2, (hw // nhead) ** -0.5, p_drop, *seed)
+    if do is None:
+        nv.attn_fwd(*ptrs(q, kv), o, lse, *tail)
+    else:
+        nv.attn_bwd(*ptrs(q, kv), do.contiguous(), lse, *ptrs(dq, dkv), *tail)
+
+
 class _AttnPacked(torch.autograd.Function):
     """Self-attention over the packed in_proj output ``qkv`` [B, 17, 3*H*32] (bf16) through the HIP kernels
     ``g2048_attn_fwd/bwd``; returns [B, 17, H*32] already in the layout out_proj reads.  The gradient is written
@@ -624,33 +601,21 @@ class _AttnPacked(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, nhead, p_drop):
-        from ..g2048 import native as nv
-
         B, S, W = qkv.shape
-        hw = W // 3
         qkv = qkv.contiguous()
-        o = torch.empty((B, S, hw), dtype=torch.bfloat16, device=qkv.device)
+        o = torch.empty((B, S, W // 3), dtype=torch.bfloat16, device=qkv.device)
         lse = torch.empty((B, nhead, S), dtype=torch.float32, device=qkv.device)
         seed = _seed_pair(qkv, p_drop)
-        base = qkv.data_ptr()
-        strides = (S * W, W) * 3
-        nv.attn_fwd(base, base + 2 * hw, base + 4 * hw, o, lse, B, nhead, S, strides, (hw // nhead) ** -0.5, p_drop, *seed)
+        _attn_launch(None, qkv, nhead, p_drop, seed, lse, o=o)
         ctx.save_for_backward(qkv, lse)
         ctx.meta = (nhead, p_drop, seed)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        from ..g2048 import native as nv
-
         qkv, lse = ctx.saved_tensors
-        nhead, p_drop, seed = ctx.meta
-        B, S, W = qkv.shape
-        hw = W // 3
         dqkv = torch.empty_like(qkv)
-        base, dbase = qkv.data_ptr(), dqkv.data_ptr()
-        nv.attn_bwd(base, base + 2 * hw, base + 4 * hw, do.contiguous(), lse, dbase, dbase + 2 * hw, dbase + 4 * hw, B,
-                    nhead, S, (S * W, W) * 3, (hw // nhead) ** -0.5, p_drop, *seed)
+        _attn_launch(None, qkv, *ctx.meta, lse, do=do, dkv=dqkv)
         return dqkv, None, None
 
 
@@ -659,33 +624,21 @@ class _AttnCls(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, kv, nhead, p_drop):
-        from ..g2048 import native as nv
-
         B, S, W = kv.shape
-        hw = W // 2
         q, kv = q.contiguous(), kv.contiguous()
-        o = torch.empty((B, 1, hw), dtype=torch.bfloat16, device=kv.device)
+        o = torch.empty((B, 1, W // 2), dtype=torch.bfloat16, device=kv.device)
         lse = torch.empty((B, nhead, 1), dtype=torch.float32, device=kv.device)
         seed = _seed_pair(kv, p_drop)
-        kb = kv.data_ptr()
-        nv.attn_fwd(q.data_ptr(), kb, kb + 2 * hw, o, lse, B, nhead, 1, (hw, 0, S * W, W, S * W, W),
-                    (hw // nhead) ** -0.5, p_drop, *seed)
+        _attn_launch(q, kv, nhead, p_drop, seed, lse, o=o)
         ctx.save_for_backward(q, kv, lse)
         ctx.meta = (nhead, p_drop, seed)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        from ..g2048 import native as nv
-
         q, kv, lse = ctx.saved_tensors
-        nhead, p_drop, seed = ctx.meta
-        B, S, W = kv.shape
-        hw = W // 2
         dq, dkv = torch.empty_like(q), torch.empty_like(kv)
-        kb, db = kv.data_ptr(), dkv.data_ptr()
-        nv.attn_bwd(q.data_ptr(), kb, kb + 2 * hw, do.contiguous(), lse, dq.data_ptr(), db, db + 2 * hw, B, nhead, 1,
-                    (hw, 0, S * W, W, S * W, W), (hw // nhead) ** -0.5, p_drop, *seed)
+        _attn_launch(q, kv, *ctx.meta, lse, do=do, dq=dq, dkv=dkv)
         return dq, dkv, None, None
 
 
@@ -696,8 +649,6 @@ class _AddLayerNorm(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, a, gamma, beta, eps, p_drop, h_link=None, pre=None):
-        from ..g2048 import native as nv
-
         ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not as a zero-filled tensor
         ctx.h_link = h_link
         if h_link is not None:
@@ -733,33 +684,43 @@ class _AddLayerNorm(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_x, g_h):
-        from ..g2048 import native as nv
-
         xn, gamma, stats = ctx.saved_tensors
         row_stride, p_drop, seed, has_a = ctx.meta
-        T = xn.numel() // 256
-        dx = torch.empty(xn.shape, dtype=torch.float32, device=xn.device)
-        da = torch.empty(xn.shape, dtype=torch.bfloat16, device=xn.device) if has_a else None
-        g_x = g_x.contiguous() if g_x is not None else None
-        sink = _sink_for(*ctx.params)
-        pend = ctx.h_link.take() if ctx.h_link is not None else None
-        if pend is not None:  # the consumer of h left its input-gradient GEMM to this node: GEMM + LayerNorm backward in one launch
-            if g_h is not None:
-                raise RuntimeError("the normalised activation has a second consumer besides the linked Linear")
-            ws = nv.linear_add_ln_bwd(pend[0], pend[1], xn.data_ptr(), row_stride, g_x, stats[0], stats[1], gamma, dx, da, p_drop, *seed,
-                                      **pend[2])
-            dparams = None if sink is not None else ws.sum(0).view(3, 256)
-        else:
-            if g_h is None:
-                g_h = torch.zeros(xn.shape, dtype=torch.bfloat16, device=xn.device)
-            dparams = None if sink is not None else torch.empty((3, 256), dtype=torch.float32, device=xn.device)
-            ws = nv.add_ln_bwd(xn.data_ptr(), row_stride, g_x, g_h.contiguous(), stats[0], stats[1], gamma, dx, da, dparams, T, p_drop,
-                               *seed)
-        if sink is not None:
-            sink.add(ctx.params[0], ws, 768, 256, ws.shape[0])
-            sink.add(ctx.params[1], ws[:, 256:], 768, 256, ws.shape[0])
-            return dx, da, None, None, None, None, None, None
-        return dx, da, dparams[0], dparams[1], None, None, None, None
+        dx, da, (dgamma, dbeta, _) = _add_ln_backward(xn.shape, xn.device, xn.data_ptr(), row_stride, g_x, g_h, stats, gamma, has_a, p_drop,
+                                                      seed, ctx.h_link, _sink_for(*ctx.params), ctx.params + (None,))
+        return dx, da, dgamma, dbeta, None, None, None, None
+
+
+def _add_ln_backward(shape, device, x_ptr, row_stride, g_x, g_h, stats, gamma, want_da, p_drop, seed, h_link, sink, params, g_x_period=1):
+    """The backward of ``h = LayerNorm(x + dropout(a))`` for the three nodes that end in it (``g2048_add_ln_bwd``; ``stats`` / ``gamma``
+    None: no LayerNorm, x_ptr 0).  ``g_x`` / ``g_h``: the gradients of the stream and of h, either may be None; a consumer of h that left
+    its input-gradient GEMM on ``h_link`` (``HLink``) gets it fused into the same launch (``g2048_linear_add_ln_bwd``) and must be h's
+    only consumer.  ``params`` = (gamma, beta, bias of the Linear that produced a) with None for what the node does not have: with a
+    ``sink`` their partial sums are registered there, in that order.  Returns (dx f32, da bf16 or None, (dgamma, dbeta, dbias) - all
+    None with a sink)."""
+    dx = torch.empty(shape, dtype=torch.float32, device=device)
+    da = torch.empty(shape, dtype=torch.bfloat16, device=device) if want_da else None
+    g_x = g_x.contiguous() if g_x is not None else None
+    mean, rstd = (None, None) if stats is None else (stats[0], stats[1])
+    pend = h_link.take() if h_link is not None else None
+    if pend is not None:  # the consumer of h left its input-gradient GEMM to this node: GEMM + LayerNorm backward in one launch
+        if g_h is not None:
+            raise RuntimeError("the normalised activation has a second consumer besides the linked Linear")
+        ws = nv.linear_add_ln_bwd(pend[0], pend[1], x_ptr, row_stride, g_x, mean, rstd, gamma, dx, da, p_drop, *seed,
+                                  g_x_period=g_x_period, **pend[2])
+        dparams = None if sink is not None else ws.sum(0).view(3, 256)
+    else:
+        if g_h is None:
+            g_h = torch.zeros(shape, dtype=torch.bfloat16, device=device)
+        dparams = None if sink is not None else torch.empty((3, 256), dtype=torch.float32, device=device)
+        ws = nv.add_ln_bwd(x_ptr, row_stride, g_x, g_h.contiguous(), mean, rstd, gamma, dx, da, dparams, dx.numel() // 256, p_drop, *seed,
+                           g_x_period=g_x_period)
+    if sink is None:
+        return dx, da, tuple(dparams)
+    for k, p in enumerate(params):  # the workspace rows are dgamma | dbeta | column sums of da
+        if p is not None:
+            sink.add(p, ws[:, 256 * k:], 768, 256, ws.shape[0])
+    return dx, da, (None, None, None)
 
 
 def _residual_rows(x: torch.Tensor):
@@ -808,8 +769,6 @@ class _LinearAddLayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, weight, bias, wb, bb, x, gamma, beta, eps, p_drop, wbT=None, link=None, cls_link=None, h_link=None,
                 w_packed=None):
-        from ..g2048 import native as nv
-
         ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not as a zero-filled tensor
         ctx.wbT, ctx.link = wbT, link
         ctx.params = (weight, bias, gamma, beta)
@@ -843,39 +802,19 @@ class _LinearAddLayerNorm(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_x, g_h):
-        from ..g2048 import native as nv
-
         u, wb, xn, gamma, stats = ctx.saved_tensors
         p_drop, seed = ctx.meta
         T = xn.numel() // 256
-        dx = torch.empty(xn.shape, dtype=torch.float32, device=xn.device)
-        da = torch.empty(xn.shape, dtype=torch.bfloat16, device=xn.device)
         weight, bias, gamma_p, beta_p = ctx.params
         sink = _sink_for(weight, bias, gamma_p, beta_p)
-        dparams = None if sink is not None else torch.empty((3, 256), dtype=torch.float32, device=xn.device)
         period = 1
         cl = ctx.cls_link
         if cl is not None and cl.g is not None:  # the stream's only gradient: the CLS rows, from _ClsRows
             if g_x is not None:
                 raise RuntimeError("the residual stream entering the CLS-only layer has a second consumer")
             g_x, period, cl.g = cl.g, xn.shape[1], None
-        pend = ctx.h_link.take() if ctx.h_link is not None else None
-        if pend is not None:  # the consumer of h left its input-gradient GEMM to this node: GEMM + LayerNorm backward in one launch
-            if g_h is not None:
-                raise RuntimeError("the normalised activation has a second consumer besides the linked Linear")
-            ws = nv.linear_add_ln_bwd(pend[0], pend[1], xn.data_ptr(), 256, None if g_x is None else g_x.contiguous(), stats[0],
-                                      stats[1], gamma, dx, da, p_drop, *seed, g_x_period=period, **pend[2])
-            if sink is None:
-                dparams = ws.sum(0).view(3, 256)
-        else:
-            if g_h is None:
-                g_h = torch.zeros(xn.shape, dtype=torch.bfloat16, device=xn.device)
-            ws = nv.add_ln_bwd(xn.data_ptr(), 256, None if g_x is None else g_x.contiguous(), g_h.contiguous(), stats[0], stats[1],
-                               gamma, dx, da, dparams, T, p_drop, *seed, g_x_period=period)
-        if sink is not None:
-            sink.add(gamma_p, ws, 768, 256, ws.shape[0])
-            sink.add(beta_p, ws[:, 256:], 768, 256, ws.shape[0])
-            sink.add(bias, ws[:, 512:], 768, 256, ws.shape[0])
+        dx, da, dparams = _add_ln_backward(xn.shape, xn.device, xn.data_ptr(), 256, g_x, g_h, stats, gamma, True, p_drop, seed, ctx.h_link,
+                                           sink, (gamma_p, beta_p, bias), g_x_period=period)
         with torch.autocast("cuda", enabled=False):
             da2, u2 = da.view(T, 256), u.reshape(T, -1)
             du = None
@@ -911,8 +850,6 @@ class _LinearAddCast(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, u, weight, bias, wb, bb, x, p_drop):
-        from ..g2048 import native as nv
-
         with torch.autocast("cuda", enabled=False):
             a = F.linear(u, wb, bb)
         ctx.params = (weight, bias)
@@ -927,22 +864,17 @@ class _LinearAddCast(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_h):
-        from ..g2048 import native as nv
-
         u, wb = ctx.saved_tensors
         p_drop, seed, shape = ctx.meta
         T = g_h.numel() // 256
-        dx = torch.empty(shape, dtype=torch.float32, device=g_h.device)
-        da = torch.empty(shape, dtype=torch.bfloat16, device=g_h.device)
         weight, bias = ctx.params
         sink = _sink_for(weight, bias)
-        dparams = None if sink is not None else torch.empty((3, 256), dtype=torch.float32, device=g_h.device)
-        ws = nv.add_ln_bwd(0, 256, None, g_h.contiguous(), None, None, None, dx, da, dparams, T, p_drop, *seed)
+        dx, da, dparams = _add_ln_backward(shape, g_h.device, 0, 256, None, g_h, None, None, True, p_drop, seed, None, sink,
+                                           (None, None, bias))
         with torch.autocast("cuda", enabled=False):
             da2, u2 = da.view(T, 256), u.reshape(T, -1)
             du = (da2 @ wb).view(u.shape) if ctx.needs_input_grad[0] else None
             if sink is not None:
-                sink.add(bias, ws[:, 512:], 768, 256, ws.shape[0])
                 _sink_weight(sink, weight, da2, u2)
                 return du, None, None, None, None, dx, None
             dw = _dweight(da2, u2)
@@ -958,8 +890,6 @@ class _LinearReluDropout(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, weight, bias, wb, bb, p_drop, link=None, h_link=None, wt_packed=None):
-        from ..g2048 import native as nv
-
         ctx.h_link, ctx.wt_packed = h_link, wt_packed  # (HLink: the producer of h may run this node's input-gradient GEMM itself)
         h2 = h.reshape(-1, h.shape[-1])
         with torch.autocast("cuda", enabled=False):
@@ -982,8 +912,6 @@ class _LinearReluDropout(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from ..g2048 import native as nv
-
         h, wb, y = ctx.saved_tensors
         link = ctx.link
         weight, bias = ctx.params
@@ -1054,8 +982,6 @@ class _EmbedBoards(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, boards, emb_weight, pe, cls, p_drop, pre=None):
-        from ..g2048 import native as nv
-
         boards = boards.contiguous()
         M = boards.shape[0]
         w = emb_weight.detach()
@@ -1078,8 +1004,6 @@ class _EmbedBoards(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from ..g2048 import native as nv
-
         (boards,) = ctx.saved_tensors
         p_drop, seed, w_dtype, c_dtype = ctx.meta
         emb_weight, cls = ctx.params
@@ -1148,8 +1072,6 @@ class TailPlan:
         self.eps, self.p_drop = float(eps), float(p_drop)
 
     def buffers(self, M: int, device):
-        from ..g2048 import native as nv
-
         key = (int(M), str(device))
         buf = self.cache.get(key)
         if buf is None or getattr(buf, "busy", False):
@@ -1164,15 +1086,11 @@ class TailPlan:
         return buf
 
     def fwd_struct(self):
-        from ..g2048 import native as nv
-
         t = {k: self.dense[k] for k in ("wo", "w1", "w2", "a1", "a2", "a3", "c1", "c2", "c3")}
         t.update({k: self.params[k].detach() for k in ("bo", "b1", "b2", "ab1", "ab2", "cb1", "cb2", "ln_g", "ln_b")})
         return nv.tail_weights(t), t
 
     def bwd_struct(self):
-        from ..g2048 import native as nv
-
         t = {k + "T": self.transposed[k] for k in ("wo", "w1", "w2", "a1", "a2", "c1", "c2")}
         t.update(a3=self.dense["a3"], c3=self.dense["c3"], ln_g=self.params["ln_g"].detach())
         return nv.tail_weights_t(t), t
@@ -1196,8 +1114,6 @@ class _ClsTailHeads(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, o, x, plan, *params):
-        from ..g2048 import native as nv
-
         M = o.shape[0]
         o2 = o.reshape(M, 256).contiguous()
         xr, row_stride = _residual_rows(x)
@@ -1218,8 +1134,6 @@ class _ClsTailHeads(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits, dvalues):
-        from ..g2048 import native as nv
-
         plan, buf = ctx.plan, ctx.buf
         M = buf.M
         dev = buf.logits.device

@@ -12,7 +12,7 @@ import torch.nn.functional as F
 from torch.distributions import Categorical
 
 from ..env_definitions import ACTION_DIM, OBS_DIM
-from .hip_ops import TAIL_PARAM_ORDER, Bf16Shadow, TailBufferCache, TailPlan, _ClsTailHeads, _linear, _train_bf16
+from .hip_ops import TAIL_PARAM_ORDER, Bf16Shadow, TailBufferCache, TailPlan, _ClsTailHeads, _env_on, _linear, _train_bf16
 from .transformer_encoder import TransformerEncoder
 
 
@@ -120,7 +120,7 @@ class PPOAgent(_ActorCritic):
     def features(self, observations):
         w = self.input_embedding.weight
         if self.transformer.embed_boards_ok(observations, w):
-            return self.transformer.forward_boards(observations, w, reduction=self.reduction)
+            return self.transformer.forward_boards(observations, w, reduction=self.reduction)[0]
         return self.transformer(self.embed(observations), reduction=self.reduction)
 
     # ---- the fused CLS tail of the update path (hip_ops._ClsTailHeads): last layer's out_proj .. both heads in one node
@@ -139,16 +139,17 @@ class PPOAgent(_ActorCritic):
         """Closure handed to the encoder (``TransformerEncoder.encode``): adds the heads' parameters and shadows to the last
         layer's and runs the node."""
         a, c = list(self.actor), list(self.critic)
-        lins = [a[0], a[2], a[4], c[0], c[2], c[4]]
+        heads = dict(a1=a[0].weight, ab1=a[0].bias, a2=a[2].weight, ab2=a[2].bias, a3=a[4].weight, c1=c[0].weight,
+                     cb1=c[0].bias, c2=c[2].weight, cb2=c[2].bias, c3=c[4].weight)  # (the order of ``_heads``' shadow)
+        at = {k: i for i, k in enumerate(heads)}
+        wide = [at[k] for k in ("a1", "a2", "c1", "c2")]  # the 512-wide matrices: fragment-packed both ways
         if self._head_shadow is None or not self._head_shadow.packed:
-            ps = [q for m in lins for q in (m.weight, m.bias) if q is not None]  # a1.w a1.b a2.w a2.b a3.w c1.w c1.b c2.w c2.b c3.w
-            self._head_shadow = Bf16Shadow(ps, packed=[0, 2, 5, 7])
+            self._head_shadow = Bf16Shadow(list(heads.values()), packed=wide, packed_t=wide)
         v = self._head_shadow()
         pv, ptv = self._head_shadow.pviews, self._head_shadow.ptviews
-        params = dict(params, a1=a[0].weight, ab1=a[0].bias, a2=a[2].weight, ab2=a[2].bias, a3=a[4].weight, c1=c[0].weight,
-                      cb1=c[0].bias, c2=c[2].weight, cb2=c[2].bias, c3=c[4].weight)
-        dense = dict(dense, a1=pv[0], a2=pv[2], a3=v[4], c1=pv[5], c2=pv[7], c3=v[9])
-        transposed = dict(transposed, a1=ptv[0], a2=ptv[2], c1=ptv[5], c2=ptv[7])
+        params = dict(params, **heads)
+        dense = dict(dense, a3=v[at["a3"]], c3=v[at["c3"]], **{k: pv[at[k]] for k in ("a1", "a2", "c1", "c2")})
+        transposed = dict(transposed, **{k: ptv[at[k]] for k in ("a1", "a2", "c1", "c2")})
         if not hasattr(self, "_tail_buffers"):
             self._tail_buffers = TailBufferCache()
         plan = TailPlan(params, dense, transposed, self._tail_buffers, eps, p_drop)
@@ -170,11 +171,8 @@ class PPOAgent(_ActorCritic):
     def forward(self, observations: torch.Tensor, action_mask: torch.Tensor = None):
         w = self.input_embedding.weight
         if self.transformer.embed_boards_ok(observations, w) and self._tail_heads_ok():
-            out = self.transformer.forward_boards(observations, w, reduction=self.reduction, tail_heads=self._tail_heads)
-            if isinstance(out, tuple):
-                logits, values = out
-            else:
-                logits, values = self._heads(out)
+            feats, heads_out = self.transformer.forward_boards(observations, w, reduction=self.reduction, tail_heads=self._tail_heads)
+            logits, values = heads_out if heads_out is not None else self._heads(feats)
             if action_mask is not None:
                 logits = logits - 1e8 * (1 - action_mask.float())
             return logits, values
@@ -242,13 +240,10 @@ class MLPAgent(_ActorCritic):
     def _update_node_ok(self, observations) -> bool:
         """The update path on packed boards at the standard shapes: the whole policy is one autograd node over ten launches
         (``mlp_ops._MLPUpdate``; G2048_MLP_FUSED=0 keeps the per-layer nodes, the A/B switch)."""
-        import os
-
         from .mlp_ops import MLPPlan
 
         return (observations.dtype == torch.uint8 and observations.dim() == 2 and observations.shape[1] == 16
-                and _train_bf16(observations, self.trunk_in.weight) and MLPPlan.supports(self)
-                and os.environ.get("G2048_MLP_FUSED", "1").strip().lower() not in ("0", "false", "no", "off"))
+                and _train_bf16(observations, self.trunk_in.weight) and MLPPlan.supports(self) and _env_on("G2048_MLP_FUSED"))
 
     def forward(self, observations: torch.Tensor, action_mask: torch.Tensor = None):
         if self._update_node_ok(observations):

@@ -30,7 +30,7 @@ from .rollout_buffer import RolloutBuffer
 from .torch_action_wrapper import TorchActionFunction, resolve_symmetry
 from . import torch_compat
 from .capture import capture as capture_graph
-from .hip_ops import Bf16Shadow, GradSink, grad_sink, graph_seed_state
+from .hip_ops import Bf16Shadow, GradSink, _env_on, grad_sink, graph_seed_state
 
 logger = logging.getLogger(__name__)
 
@@ -327,7 +327,7 @@ class PPOTrainer:
         # flat buffers on the device; anything else (Adam, CPU) takes the PyTorch calls of the reference, and so does everything
         # with G2048_FLAT_OPT=0 (the A/B switch)
         self._flat_step = None
-        if os.environ.get("G2048_FLAT_OPT", "1").strip().lower() not in ("0", "false", "no", "off"):
+        if _env_on("G2048_FLAT_OPT"):
             self._flat_step = flat_step_for(self.optimizer, self.device, first=self._early_params)
         if self.world > 1 or self._flat_step is not None:
             self._bind_flat_grads()
@@ -345,8 +345,7 @@ class PPOTrainer:
                              and getattr(self.agent, "hip_graph_safe", False))
         self.use_hip_graph = bool(use_hip_graph) and self.device.type == "cuda"
         # second stage of all gradient reductions in one launch (GradSink); needs the flat gradient bucket
-        self.grad_sink = self.device.type == "cuda" and \
-            os.environ.get("G2048_GRAD_SINK", "1").strip().lower() not in ("0", "false", "no", "off")
+        self.grad_sink = self.device.type == "cuda" and _env_on("G2048_GRAD_SINK")
         self._graphs = {}
         self._rollout_graphs = {}  # captured rollout forwards of agents that ask for it (``rollout_graph_ok``: the MLP policy)
         self.hip_graph_fallback = None  # repr of the exception that made _build_graph drop to the eager update

@@ -280,6 +280,84 @@ def test_bf16_shadow_copies_start_cold():
         assert torch.equal(c.sh()[0], c.lin.weight.detach().to(torch.bfloat16)) and not c.sh.maintained()
 
 
+def _spec_table(num_layers, transposed=(), packed=(), packed_t=()):
+    """{(layer, Linear): set of copies} from three lists of (Linear, layers) - the literal form the tables below are written in."""
+    table = {(i, n): set() for i in range(num_layers) for n in ("in_proj", "out_proj", "linear1", "linear2")}
+    for copy, entries in (("transposed", transposed), ("packed", packed), ("packed_t", packed_t)):
+        for name, layers in entries:
+            for i in layers:
+                table[i, name].add(copy)
+    return table
+
+
+def test_encoder_shadow_spec_tables():
+    """What the encoder asks of its bf16 shadow, against literal tables written out from the index lists this function replaced
+    (transposed = 8i+6 for every layer and 8i+2 in front of the last; packed both ways = 8 last + 2, 4, 6; at d_model 256, in front
+    of the last: packed 8i+2, 8i+6 and packed transposes 8i+0, 8i+4, and 8 last + 0 when last >= 1)."""
+    from src.ppo.transformer_encoder import LINEARS, encoder_shadow_spec
+
+    assert LINEARS == ("in_proj", "out_proj", "linear1", "linear2")  # the order of a layer's parameters in the shadow
+    cases = {
+        (4, 256): _spec_table(4, transposed=[("linear2", (0, 1, 2, 3)), ("out_proj", (0, 1, 2))],
+                              packed=[("out_proj", (0, 1, 2, 3)), ("linear2", (0, 1, 2, 3)), ("linear1", (3,))],
+                              packed_t=[("in_proj", (0, 1, 2, 3)), ("linear1", (0, 1, 2, 3)), ("out_proj", (3,)), ("linear2", (3,))]),
+        (1, 256): _spec_table(1, transposed=[("linear2", (0,))],
+                              packed=[("out_proj", (0,)), ("linear1", (0,)), ("linear2", (0,))],
+                              packed_t=[("out_proj", (0,)), ("linear1", (0,)), ("linear2", (0,))]),
+        (4, 128): _spec_table(4, transposed=[("linear2", (0, 1, 2, 3)), ("out_proj", (0, 1, 2))],
+                              packed=[("out_proj", (3,)), ("linear1", (3,)), ("linear2", (3,))],
+                              packed_t=[("out_proj", (3,)), ("linear1", (3,)), ("linear2", (3,))]),
+    }
+    for (n, d), want in cases.items():
+        spec = encoder_shadow_spec(n, d)
+        assert len(spec) == n and all(set(row) == set(LINEARS) for row in spec), (n, d)
+        got = {(i, name): set(row[name]) for i, row in enumerate(spec) for name in LINEARS}
+        assert got == want, (n, d, {k: (got[k], want[k]) for k in want if got[k] != want[k]})
+    one, small = encoder_shadow_spec(1, 256), encoder_shadow_spec(4, 128)
+    assert not one[0]["in_proj"] and "transposed" not in one[0]["out_proj"]  # no in_proj^T, no out_proj^T
+    assert all(not (row[name] & {"packed", "packed_t"}) for row in small[:3] for name in LINEARS) and not small[3]["in_proj"]
+
+
+class _PackedShadowOwner(torch.nn.Module):  # (module level: pickle needs an importable class)
+    def __init__(self, **request):
+        super().__init__()
+        from src.ppo.hip_ops import Bf16Shadow
+
+        self.lins = torch.nn.ModuleList(torch.nn.Linear(32, 64) for _ in range(4))
+        self.sh = Bf16Shadow([p for m in self.lins for p in (m.weight, m.bias)], **request)
+
+
+@pytest.mark.parametrize("request_", [dict(transposed=(0,), packed=(2,), packed_t=(4,)),  # disjoint
+                                      dict(transposed=(0, 2), packed=(2, 4), packed_t=(4, 6, 0)),  # overlapping
+                                      dict(packed=(0, 6), packed_t=(0, 6)), dict()])
+def test_bf16_shadow_three_orthogonal_requests(request_):
+    """``transposed`` / ``packed`` / ``packed_t`` are independent: exactly the asked indices appear in ``tviews`` / ``pviews`` /
+    ``ptviews``, each copy holds what its name says, and a pickle round trip asks the same of the copied parameters."""
+    import pickle
+
+    from src.g2048 import native as nv
+
+    m = _PackedShadowOwner(**request_)
+    assert m.sh.tviews == {} and m.sh.pviews == {} and m.sh.ptviews == {}  # nothing exists before the first use
+    for owner in (m, pickle.loads(pickle.dumps(m))):
+        sh = owner.sh
+        views = sh()
+        assert set(sh.tviews) == set(request_.get("transposed", ())) and sh.transposed == tuple(request_.get("transposed", ()))
+        assert set(sh.pviews) == set(request_.get("packed", ())) and set(sh.ptviews) == set(request_.get("packed_t", ()))
+        # ``packed``: the indices packed BOTH ways (what PPOAgent._tail_heads tests to see whether a shadow has packed copies)
+        assert set(sh.packed) == set(sh.pviews) & set(sh.ptviews)
+        for i, p in enumerate(sh.params):
+            ref = p.detach().to(torch.bfloat16)
+            assert p is list(owner.lins)[i // 2].weight or p is list(owner.lins)[i // 2].bias
+            assert torch.equal(views[i], ref)
+            if i in sh.tviews:
+                assert torch.equal(sh.tviews[i], ref.t())
+            if i in sh.pviews:
+                assert torch.equal(sh.pviews[i], nv.pack_fragments(ref))
+            if i in sh.ptviews:
+                assert torch.equal(sh.ptviews[i], nv.pack_fragments(ref.t()))
+
+
 def test_capture_guard_keeps_the_collector_off_and_restores_it():
     """capture.no_gc_during_capture: collect first, cyclic collector off inside, previous state restored (also on error);
     CollectionsWhileCapturing sees collections (none of them 'while capturing' on a CPU box)."""
