@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Train the n-tuple afterstate value network by TD(0) and report its strength on the README protocol.
+"""Train the n-tuple afterstate value network by TD(0) or TC and report its strength on the README protocol.
 
     python 2048-ppo-agent_amd/run/train_ntuple.py --envs 4096 --minutes 10 --evals 3 --out result.json
+    python 2048-ppo-agent_amd/run/train_ntuple.py --learner tc --alpha 1.0 --envs 4096 --minutes 10 --evals 3
 
 Training = ``NTupleTrainer`` on ``--envs`` always-live boards, greedy in the network being learned, in chunks of lock-steps; after
 every chunk one byte per env is read back (the largest tile on a training board).  "First 2048" is the training wall-clock and
@@ -9,6 +10,8 @@ the lock-step count at the end of the first chunk after which a training board h
 protocol of ``evaluate_max_tile`` (``--eval-episodes`` episodes, seed 42, batches of 100, largest tile of the final board), at
 ``--evals`` points spread evenly over the budget, the last one at its end; evaluation time is excluded from the training clock.
 ``--eval-plies 0 1 2`` plays every evaluation point once per listed expectimax depth over the network (0: greedy, the default).
+``--learner tc`` learns by temporal coherence (a step size per table entry, ``NTupleTrainer``); it is meant to run at ``--alpha 1.0``
+and records the coherence numbers (entries with a rate, their mean rate) at every evaluation point.
 """
 import argparse
 import json
@@ -30,6 +33,7 @@ def main():
     ap.add_argument("--envs", type=int, default=4096, help="parallel boards")
     ap.add_argument("--minutes", type=float, default=10.0, help="training budget (wall-clock, evaluation excluded)")
     ap.add_argument("--alpha", type=float, default=0.1, help="learning rate of the whole network (split over its 8 m lookups)")
+    ap.add_argument("--learner", choices=NTupleTrainer.LEARNERS, default="td0", help="td0: one alpha for every entry; tc: a rate per entry")
     ap.add_argument("--evals", type=int, default=3, help="evaluation points, evenly spread, the last at the end of the budget")
     ap.add_argument("--eval-at", type=float, nargs="*", default=None, help="evaluation points in minutes instead of --evals")
     ap.add_argument("--eval-episodes", type=int, default=1000)
@@ -44,11 +48,11 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     net = NTupleNetwork(device=dev)
-    trainer = NTupleTrainer(net, args.envs, alpha=args.alpha, seed=args.seed, device=dev)
+    trainer = NTupleTrainer(net, args.envs, alpha=args.alpha, seed=args.seed, device=dev, learner=args.learner)
     budget = args.minutes * 60.0
     points = sorted(60.0 * m for m in args.eval_at) if args.eval_at else [budget * (k + 1) / args.evals for k in range(max(args.evals, 1))]
-    result = dict(envs=args.envs, alpha=args.alpha, seed=args.seed, tuples=[list(t) for t in net.tuples], frac_bits=net.frac_bits,
-                  minutes=args.minutes, first_2048=None, evaluations=[])
+    result = dict(envs=args.envs, learner=args.learner, alpha=args.alpha, seed=args.seed, tuples=[list(t) for t in net.tuples],
+                  frac_bits=net.frac_bits, minutes=args.minutes, first_2048=None, evaluations=[])
     trained = 0.0
     episodes = 0
     while points:
@@ -62,10 +66,17 @@ def main():
             print(f"first 2048 tile on a training board after {trained:.1f} s, {trainer.lock_steps} lock-steps", flush=True)
         if trained >= points[0]:
             points.pop(0)
+            coherence = None
+            if args.learner == "tc":
+                c = trainer.coherence()
+                coherence = dict(entries=int(c["entries"].item()), mean_rate=round(float(c["mean_rate"].item()), 4))
+                print(f"{trained / 60:.2f} min: {coherence['entries']} entries with a rate, mean rate {coherence['mean_rate']}", flush=True)
             for plies in args.eval_plies:
                 ev = evaluate_ntuple(net, dev, num_episodes=args.eval_episodes, seed=42, plies=plies)
                 ev.update(plies=plies, train_seconds=round(trained, 2), lock_steps=trainer.lock_steps, episodes_trained=episodes,
                           max_abs_weight=int(net.weights.abs().max().item()))
+                if coherence is not None:
+                    ev.update(coherence=coherence)
                 result["evaluations"].append(ev)
                 print(f"{trained / 60:.2f} min, {trainer.lock_steps} lock-steps, plies {plies}: mean max tile "
                       f"{ev['mean_max_tile']:.1f}, percent {ev['percent']}", flush=True)

@@ -520,6 +520,32 @@ def ntuple_td_apply(prev_after, flag, tuple_cells, weights, acc, cnt):
            "g2048_ntuple_td_apply")
 
 
+def ntuple_tc_accumulate(prev_after, flag, target, weights, tuple_cells, frac_bits: int, alpha: float, acc, abs_acc, cnt,
+                         td_error=None):
+    """The accumulate half of one TC lock-step: acc i64 [m, 16^L] += delta, abs_acc i64 [m, 16^L] += |delta|, cnt i32 [m, 16^L] += 1
+    at the entries of every env with flag != 0.  td_error f32 [B] or None."""
+    cells, m, L = _tuple_cells(tuple_cells)
+    B, E = flag.numel(), m * 16 ** L
+    _check(load().g2048_ntuple_tc_accumulate(_dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"),
+                                             _dev(target, f32, B, "target"), B, _dev(weights, i32, E, "weights"), cells.ctypes.data,
+                                             m, L, int(frac_bits), float(alpha), _dev(acc, i64, E, "acc"),
+                                             _dev(abs_acc, i64, E, "abs_acc"), _dev(cnt, i32, E, "cnt"),
+                                             _dev(td_error, f32, B, "td_error", optional=True), _stream()),
+           "g2048_ntuple_tc_accumulate")
+
+
+def ntuple_tc_apply(prev_after, flag, tuple_cells, weights, acc, abs_acc, cnt, coh_e, coh_a):
+    """The apply half: every entry the same boards hit moves by its rounded mean delta times its rate |coh_e| / coh_a (rate 1
+    where coh_a == 0), coh_e += the mean, coh_a += the mean magnitude, acc = abs_acc = cnt = 0 there."""
+    cells, m, L = _tuple_cells(tuple_cells)
+    B, E = flag.numel(), m * 16 ** L
+    _check(load().g2048_ntuple_tc_apply(_dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"), B, cells.ctypes.data,
+                                        m, L, _dev(weights, i32, E, "weights"), _dev(acc, i64, E, "acc"),
+                                        _dev(abs_acc, i64, E, "abs_acc"), _dev(cnt, i32, E, "cnt"), _dev(coh_e, i32, E, "coh_e"),
+                                        _dev(coh_a, i32, E, "coh_a"), _stream()),
+           "g2048_ntuple_tc_apply")
+
+
 def ntuple_link(tr_boards_row, tr_meta_row, prev_after, flag):
     """prev_after u8 [B,16] = the afterstate of the move recorded in one trajectory row, flag u8 [B] = 2 where it ended the episode."""
     B = flag.numel()

@@ -172,9 +172,22 @@ class NTupleTrainer:
     (``use_mask=1, sample=0``, a one-row trajectory) -> ``link``, which replays the recorded move to get the new afterstate and
     reads the done bit.  The key chain advances as in ``RolloutEngine.rollout_policy_fixed``: the init split at the first call,
     then two sub-keys per lock-step.  Nothing is read back inside the loop; env state and learner state persist across calls.
+
+    ``learner="tc"`` replaces the middle pair by ``tc_accumulate`` -> ``tc_apply`` (temporal-coherence learning): every table entry
+    moves by its mean delta times its own rate ``|coh_e| / coh_a``, the sum of its past updates over the sum of their magnitudes
+    (rate 1 while ``coh_a == 0``), all in integer arithmetic, so a run stays reproducible bit for bit.  ``alpha`` keeps its default
+    of 0.1, but TC is meant to run at ``alpha=1.0``: the rates take the step size down where updates disagree.  It adds ``abs_acc``
+    (i64), ``coh_e`` and ``coh_a`` (i32) to ``acc`` and ``cnt``: at the default network the trainer then holds about 2.3 GB of tables
+    (weights 0.27, acc and abs_acc 0.54 each, cnt, coh_e and coh_a 0.27 each) where ``"td0"`` holds 1.07 GB.  Anything but ``"td0"``
+    or ``"tc"`` raises ``ValueError`` before a device is touched.
     """
 
-    def __init__(self, network: NTupleNetwork, num_envs: int, alpha: float = 0.1, seed: int = 0, rng_mode=None, device=None):
+    LEARNERS = ("td0", "tc")
+
+    def __init__(self, network: NTupleNetwork, num_envs: int, alpha: float = 0.1, seed: int = 0, rng_mode=None, device=None,
+                 learner: str = "td0"):
+        if learner not in self.LEARNERS:
+            raise ValueError(f"learner must be one of {self.LEARNERS}, got {learner!r}")
         if not isinstance(network, NTupleNetwork):
             raise ValueError(f"network must be an NTupleNetwork, got {type(network).__name__}")
         if int(num_envs) < 1:
@@ -192,6 +205,12 @@ class NTupleTrainer:
         u8, f32 = torch.uint8, torch.float32
         self.acc = torch.zeros(network.weights.shape, dtype=torch.int64, device=dev)
         self.cnt = torch.zeros(network.weights.shape, dtype=torch.int32, device=dev)
+        self.learner = learner
+        self.abs_acc = self.coh_e = self.coh_a = None
+        if learner == "tc":
+            self.abs_acc = torch.zeros(network.weights.shape, dtype=torch.int64, device=dev)
+            self.coh_e = torch.zeros(network.weights.shape, dtype=torch.int32, device=dev)
+            self.coh_a = torch.zeros(network.weights.shape, dtype=torch.int32, device=dev)
         self.prev_after = torch.zeros((B, 16), dtype=u8, device=dev)
         self.flag = torch.zeros(B, dtype=u8, device=dev)
         self.boards = torch.empty((B, 16), dtype=u8, device=dev)
@@ -230,9 +249,15 @@ class NTupleTrainer:
                        targets=torch.empty((T, B), dtype=torch.float32, device=self.device))
         for t in range(T):
             nv.ntuple_scores(self.boards, net.weights, net.cells, net.frac_bits, self.scores, self.targets)
-            nv.ntuple_td_accumulate(self.prev_after, self.flag, self.targets, net.weights, net.cells, net.frac_bits, self.alpha,
-                                    self.acc, self.cnt, self.td_error)
-            nv.ntuple_td_apply(self.prev_after, self.flag, net.cells, net.weights, self.acc, self.cnt)
+            if self.learner == "tc":
+                nv.ntuple_tc_accumulate(self.prev_after, self.flag, self.targets, net.weights, net.cells, net.frac_bits, self.alpha,
+                                        self.acc, self.abs_acc, self.cnt, self.td_error)
+                nv.ntuple_tc_apply(self.prev_after, self.flag, net.cells, net.weights, self.acc, self.abs_acc, self.cnt, self.coh_e,
+                                   self.coh_a)
+            else:
+                nv.ntuple_td_accumulate(self.prev_after, self.flag, self.targets, net.weights, net.cells, net.frac_bits, self.alpha,
+                                        self.acc, self.cnt, self.td_error)
+                nv.ntuple_td_apply(self.prev_after, self.flag, net.cells, net.weights, self.acc, self.cnt)
             nv.policy_step_autoreset(subs[2 * t], subs[2 * t + 1], self.scores, self.targets, True, False, 0, self.boards, self.masks,
                                      self.ep_len, tr["boards"], tr["meta"], tr["rewards"], tr["logp"], tr["values"], B, 0,
                                      self.rng_mode)
@@ -249,3 +274,39 @@ class NTupleTrainer:
         if rec is not None:
             out.update(rec)
         return out
+
+    def state_dict(self) -> dict:
+        """The learner's own state (host tensors): ``learner``, ``alpha``, ``lock_steps`` and, for ``"tc"``, ``coh_e`` / ``coh_a``, so
+        that a resumed run keeps its rates.  The weights are the network's (``NTupleNetwork.save``); the envs start afresh."""
+        out = {"learner": self.learner, "alpha": self.alpha, "lock_steps": self.lock_steps}
+        if self.learner == "tc":
+            out.update(coh_e=self.coh_e.cpu().clone(), coh_a=self.coh_a.cpu().clone())
+        return out
+
+    def load_state_dict(self, state: dict) -> None:
+        """``ValueError`` for another learner's state or tables of another shape or dtype; nothing is changed then."""
+        if state.get("learner") != self.learner:
+            raise ValueError(f"the state is of learner {state.get('learner')!r}, the trainer's is {self.learner!r}")
+        tables = {}
+        if self.learner == "tc":
+            for k in ("coh_e", "coh_a"):
+                t = state.get(k)
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(self.coh_e.shape) or t.dtype != torch.int32:
+                    raise ValueError(f"{k} of shape {None if t is None else tuple(t.shape)} does not fit tuples {self.network.tuples}")
+                tables[k] = t
+        alpha = float(state["alpha"])
+        if not (alpha > 0.0 and np.isfinite(alpha)):
+            raise ValueError(f"alpha must be a finite positive number, got {state['alpha']!r}")
+        self.alpha, self.lock_steps = alpha, int(state["lock_steps"])
+        for k, t in tables.items():
+            getattr(self, k).copy_(t)
+
+    @torch.no_grad()
+    def coherence(self) -> dict:
+        """``learner="tc"`` -> {"entries": i64 [] entries with coh_a > 0, "mean_rate": f64 [] mean of |coh_e| / coh_a over them (0 if
+        there is none)} as device tensors.  Torch reductions over the whole tables: for logging between chunks, not inside the loop."""
+        if self.learner != "tc":
+            raise ValueError(f"coherence() is of learner 'tc', the trainer's is {self.learner!r}")
+        entries = (self.coh_a > 0).sum()
+        rate = self.coh_e.abs().double() / self.coh_a.clamp(min=1).double()  # |coh_e| <= coh_a: 0 where coh_a == 0
+        return {"entries": entries, "mean_rate": rate.sum() / entries.clamp(min=1).double()}

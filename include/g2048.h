@@ -469,6 +469,39 @@ int g2048_ntuple_expectimax(const uint8_t *boards, int64_t B, const int32_t *wei
                             int L, int frac_bits, int plies, double gamma, float *workspace, float *scores, float *values,
                             void *stream);
 
+/* ---- n-tuple TC learning (temporal coherence: every table entry has its own step size, all of it integer arithmetic) ----
+ * A second learner for the n-tuple network above, in place of the td_accumulate / td_apply pair of a lock-step.  prev_after,
+ * flag, target, e, c and delta are exactly those of TD(0).  Two more tables next to weights, coh_e i32[m][16^L] and coh_a
+ * i32[m][16^L] (E and A below, all-zero at the start: rate 1), and one more accumulator, abs_acc i64[m][16^L]:
+ *   accumulate: for every env with flag != 0, every view g and tuple t: acc += delta, abs_acc += |delta|, cnt += 1;
+ *   apply: for every entry with n = cnt > 0:
+ *     d = rdiv(acc, n), a = rdiv(abs_acc, n)                      (a >= |d| because |acc| <= abs_acc)
+ *     step = A == 0 ? d : rdiv(d * |E|, A)                        (the rate |E| / A is read before the entry's own update;
+ *                                                                  |d| <= 2^30 and |E| <= A < 2^31: the product is < 2^61)
+ *     weights = sat_int32(weights + step);  E += d;  A += a       (in int64)
+ *     if A >= 2^31: E = sign(E) * (|E| / 2), A = A >> 1           (once suffices, A < 2^31 + 2^30; keeps |E| <= A < 2^31)
+ *     acc = abs_acc = cnt = 0.
+ * From all-zero coh_e and coh_a one lock-step moves the weights exactly as TD(0) does.  acc, abs_acc and cnt are all-zero
+ * between lock-steps.  Every accumulation is an integer one: the result does not depend on scheduling. */
+
+/* The accumulate half.  Operands as g2048_ntuple_td_accumulate plus abs_acc; weights are only read.  td_error f32[B] (may be
+ * NULL) = e, 0 where flag == 0.  One lane per env: 8 m gathers, then 16 m 64-bit and 8 m 32-bit atomic adds.
+ * G2048_EINVAL: a null pointer other than td_error, B outside 1 .. 2^28, the network or frac_bits as for g2048_ntuple_values,
+ * alpha not a finite positive number, prev_after not 16-byte aligned, acc or abs_acc not 8-byte aligned, target, weights, cnt
+ * or td_error not 4-byte aligned. */
+int g2048_ntuple_tc_accumulate(const uint8_t *prev_after, const uint8_t *flag, const float *target, int64_t B,
+                               const int32_t *weights, const uint8_t *tuple_cells /*host*/, int m, int L, int frac_bits, double alpha,
+                               int64_t *acc, int64_t *abs_acc, int32_t *cnt, float *td_error, void *stream);
+
+/* The apply half, in a launch of its own after g2048_ntuple_tc_accumulate on the same prev_after and flag: cnt is exchanged for
+ * 0 at the entries of the same boards and the one lane that finds cnt > 0 updates weights, coh_e, coh_a and clears acc and
+ * abs_acc there.  The tables are never scanned.
+ * G2048_EINVAL: a null pointer, B outside 1 .. 2^28, the network as above, prev_after not 16-byte aligned, acc or abs_acc not
+ * 8-byte aligned, weights, cnt, coh_e or coh_a not 4-byte aligned. */
+int g2048_ntuple_tc_apply(const uint8_t *prev_after, const uint8_t *flag, int64_t B, const uint8_t *tuple_cells /*host*/, int m, int L,
+                          int32_t *weights, int64_t *acc, int64_t *abs_acc, int32_t *cnt, int32_t *coh_e, int32_t *coh_a,
+                          void *stream);
+
 /* ---- policy network (update): attention for 17-token sequences ------------------------------------- */
 
 /* softmax(q k^T * scale) v with attention dropout, head_dim 32, Sk = 17 keys, Sq = 17 queries (or 1: the CLS row

@@ -15,6 +15,9 @@ tools/probe_mc.py).
       random play, next to the greedy-agent and one-ply lock-steps of a fresh-weights PPOAgent on the same boards.
   (d) learning speed: mean max tile over ``--episodes`` evaluation episodes (seed 42) after ``--learn-steps`` lock-steps at 1 024,
       4 096 and 65 536 envs, from zero weights, one seed each.
+``--tc`` adds the TC learner (``NTupleTrainer(learner="tc")``, alpha 1.0) under the key "tc": its two launches tc_accumulate and
+tc_apply timed as td_accumulate and td_apply are in (a), in the same two board states of a TC trainer, and its training lock-step as
+in (b).  Without it the output is unchanged.
 Prints one JSON line.
 """
 import argparse
@@ -92,6 +95,59 @@ def kernel_state(trainer, label, repeats):
     return res
 
 
+def tc_kernel_state(trainer, label, repeats):
+    """The two TC kernels on the trainer's current boards / prev_after / flag, timed as td_accumulate / td_apply are."""
+    net = trainer.network
+    w, cells, F, m = net.weights, net.cells, net.frac_bits, net.m
+    saved = w.clone(), trainer.coh_e.clone(), trainer.coh_a.clone()
+
+    def zero():
+        trainer.acc.zero_(), trainer.abs_acc.zero_(), trainer.cnt.zero_()
+
+    def accumulate():
+        nv.ntuple_tc_accumulate(trainer.prev_after, trainer.flag, trainer.targets, w, cells, F, trainer.alpha, trainer.acc, trainer.abs_acc,
+                                trainer.cnt, trainer.td_error)
+
+    def prepare_apply():
+        zero(), accumulate()
+
+    nv.ntuple_scores(trainer.boards, w, cells, F, trainer.scores, trainer.targets)
+    zero(), accumulate()
+    live = int((trainer.flag != 0).sum().item())
+    distinct = int((trainer.cnt > 0).sum().item())
+    res = {"state": label, "boards": trainer.num_envs, "envs_with_predecessor": live, "distinct_entries_hit": distinct,
+           "max_same_address_atomics": int(trainer.cnt.max().item()),
+           "per_launch": {"tc_accumulate": f"{8 * m * live} gathers, {16 * m * live} 64-bit + {8 * m * live} 32-bit atomic adds",
+                          "tc_apply": f"{8 * m * live} atomic exchanges, one read-modify-write of weights, acc, abs_acc, coh_e and coh_a "
+                                      f"per distinct entry ({distinct})"}}
+    res["tc_accumulate"] = timed(accumulate, repeats, setup=zero)
+    res["tc_apply"] = timed(lambda: nv.ntuple_tc_apply(trainer.prev_after, trainer.flag, cells, w, trainer.acc, trainer.abs_acc,
+                                                       trainer.cnt, trainer.coh_e, trainer.coh_a), repeats, setup=prepare_apply)
+    w.copy_(saved[0]), trainer.coh_e.copy_(saved[1]), trainer.coh_a.copy_(saved[2])  # the timed applies moved them
+    zero()
+    return res
+
+
+def tc_probe(boards, envs, dev, repeats, train_steps, chunk=50):
+    out = {"learner": "tc, alpha 1.0", "kernels": [], "training_lock_step": []}
+    for B in boards:
+        trainer = NTupleTrainer(NTupleNetwork(device=dev), B, alpha=1.0, device=dev, learner="tc")
+        trainer.train(1)
+        out["kernels"].append(tc_kernel_state(trainer, "reset: one lock-step after a reset of all boards", repeats))
+        trainer.train(train_steps - 1)
+        out["kernels"].append(tc_kernel_state(trainer, f"trained: {train_steps} lock-steps into training", repeats))
+        print(json.dumps(out["kernels"][-2:]), flush=True)
+        del trainer
+    for B in envs:
+        trainer = NTupleTrainer(NTupleNetwork(device=dev), B, alpha=1.0, device=dev, learner="tc")
+        t = timed(lambda: trainer.train(chunk), repeats)
+        out["training_lock_step"].append({"envs": B, "lock_steps_per_call": chunk,
+                                          **{k.replace("_ms", "_ms_per_lock_step"): round(v / chunk, 4) for k, v in t.items()}})
+        print(json.dumps(out["training_lock_step"][-1]), flush=True)
+        del trainer
+    return out
+
+
 def kernel_probe(B, dev, repeats, train_steps):
     net = NTupleNetwork(device=dev)
     trainer = NTupleTrainer(net, B, device=dev)
@@ -142,6 +198,7 @@ def main():
     ap.add_argument("--episodes", type=int, default=200)
     ap.add_argument("--board-steps", type=int, default=48)
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--tc", action="store_true", help="also time the TC learner's two launches and its training lock-step")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -168,6 +225,8 @@ def main():
     for B in a.envs:
         res["learning"].append(learning_probe(B, dev, a.learn_steps, a.episodes))
         print(json.dumps(res["learning"][-1]), flush=True)
+    if a.tc:
+        res["tc"] = tc_probe(a.boards, a.envs, dev, a.repeats, a.train_steps)
     print(json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)) or ".", exist_ok=True)
