@@ -819,6 +819,72 @@ def ppo_loss(logits, values, actions, mask_bits, old_logp, adv, ret, clip_eps: f
     return new_logp, sums, dlogits, dvalues
 
 
+def distill_loss_workspace_floats(M: int) -> int:
+    """The f32 elements of workspace ``distill_loss`` needs for M samples; raises outside 1 .. G2048_PPO_LOSS_MAX_BATCH."""
+    n = int(load().g2048_distill_loss_workspace_floats(int(M)))
+    if n < 0:
+        raise NativeError(f"distill_loss: M={M} is outside 1 .. {CONSTANTS['G2048_PPO_LOSS_MAX_BATCH']}")
+    return n
+
+
+def distill_loss(logits, values, mask_bits, teacher_q, value_target, tau: float, c_value: float, c_entropy: float, grad_scale=None,
+                 running=None, workspace=None, out=None):
+    """-> (new_logp f32 [M], sums f32 [5], dlogits like logits, dvalues like values or None); see g2048_distill_loss.  ``values``
+    and ``value_target`` are None together (no critic term).  ``grad_scale`` / ``running`` as in ``ppo_loss``; ``workspace``: f32
+    of ``distill_loss_workspace_floats(M)`` elements (allocated if None); ``out``: pre-allocated (new_logp, sums, dlogits, dvalues)."""
+    if not isinstance(teacher_q, torch.Tensor) or not teacher_q.is_cuda:
+        raise NativeError(f"teacher_q: expected a HIP device tensor, got {getattr(teacher_q, 'device', None)} (no CPU path exists)")
+    M = teacher_q.numel() // 4
+    if (values is None) != (value_target is None):
+        raise NativeError("distill_loss: values and value_target are given together or not at all")
+    for name, t in (("logits", logits), ("values", values)):
+        if t is None:
+            continue
+        if not t.is_cuda or t.dtype not in (torch.bfloat16, f32) or not t.is_contiguous():
+            raise NativeError(f"{name}: expected a contiguous bf16/f32 device tensor, got {t.dtype} on {t.device}")
+    if logits.numel() != 4 * M or (values is not None and values.numel() != M):
+        raise NativeError(f"distill_loss: logits {tuple(logits.shape)} / values "
+                          f"{None if values is None else tuple(values.shape)} do not match M={M}")
+    n_ws = distill_loss_workspace_floats(M)
+    if workspace is None:
+        workspace = torch.empty(n_ws, dtype=f32, device=logits.device)
+    if out is None:
+        out = (torch.empty(M, dtype=f32, device=logits.device), torch.empty(5, dtype=f32, device=logits.device),
+               torch.empty_like(logits), None if values is None else torch.empty_like(values))
+    new_logp, sums, dlogits, dvalues = out
+    if dlogits.dtype != logits.dtype or not dlogits.is_cuda or dlogits.numel() < 4 * M or not dlogits.is_contiguous():
+        raise NativeError("dlogits: expected a contiguous device tensor like logits")
+    if (dvalues is None) != (values is None) or (dvalues is not None and (
+            dvalues.dtype != values.dtype or not dvalues.is_cuda or dvalues.numel() < M or not dvalues.is_contiguous())):
+        raise NativeError("dvalues: expected a contiguous device tensor like values (None with it)")
+    _check(load().g2048_distill_loss(
+        logits.data_ptr(), int(logits.dtype == torch.bfloat16), None if values is None else values.data_ptr(),
+        int(values is not None and values.dtype == torch.bfloat16), _dev(mask_bits, u8, M, "mask_bits", optional=True),
+        _dev(teacher_q, f32, 4 * M, "teacher_q"), _dev(value_target, f32, M, "value_target", optional=True), M, float(tau),
+        float(c_value), float(c_entropy), _dev(new_logp, f32, M, "new_logp"), _dev(sums, f32, 5, "sums"), dlogits.data_ptr(),
+        None if dvalues is None else dvalues.data_ptr(), _dev(grad_scale, f32, 1, "grad_scale", optional=True),
+        _dev(running, torch.float64, 5, "running", optional=True), _dev(workspace, f32, n_ws, "workspace"), _stream()),
+        "g2048_distill_loss")
+    return new_logp, sums, dlogits, dvalues
+
+
+def distill_gather(idx, boards, masks, teacher_q, value_target=None, out=None):
+    """-> dict(obs u8 [M,16], masks u8 [M], q f32 [M,4], vt f32 [M] or None) = rows idx (clamped) of the imitation ring; ``out``:
+    pre-allocated tensors of that layout.  See g2048_distill_gather."""
+    M, N = idx.numel(), masks.numel()
+    dev = boards.device
+    if out is None:
+        out = dict(obs=torch.empty((M, 16), dtype=u8, device=dev), masks=torch.empty(M, dtype=u8, device=dev),
+                   q=torch.empty((M, 4), dtype=f32, device=dev),
+                   vt=None if value_target is None else torch.empty(M, dtype=f32, device=dev))
+    _check(load().g2048_distill_gather(
+        _dev(idx, i64, M, "idx"), M, N, _dev(boards, u8, 16 * N, "boards"), _dev(masks, u8, N, "masks"),
+        _dev(teacher_q, f32, 4 * N, "teacher_q"), _dev(value_target, f32, N, "value_target", optional=True),
+        _dev(out["obs"], u8, 16 * M, "o_boards"), _dev(out["masks"], u8, M, "o_masks"), _dev(out["q"], f32, 4 * M, "o_q"),
+        _dev(out.get("vt"), f32, M, "o_vt", optional=True), _stream()), "g2048_distill_gather")
+    return out
+
+
 def linear_ok(x2: torch.Tensor, weight: torch.Tensor) -> bool:
     """Shapes/strides g2048_linear_bf16 takes: x2 [T, K] and weight [N, K] bf16 on the device with contiguous rows."""
     return (x2.is_cuda and x2.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and x2.dim() == 2

@@ -1,4 +1,5 @@
 from .data_loader import create_ppo_dataloader
+from .distill import DistillTrainer
 from .expectimax import ExpectimaxActionFunction
 from .lookahead import LookaheadActionFunction
 from .monte_carlo import MonteCarloActionFunction

@@ -644,6 +644,43 @@ int g2048_ppo_loss(const void *logits, int logits_bf16, const void *values, int 
                    float clip_eps, float c_value, float c_entropy, float *new_logp, float *sums, void *dlogits,
                    void *dvalues, const float *grad_scale, double *running, void *stream);
 
+/* ---- imitation update: loss ---------------------------------------------------------------------------------
+ * Cross-entropy of the policy to a teacher's action scores (no reference counterpart: the reference only trains by PPO).  Per
+ * sample, with z_j = logit_j, or logit_j - 1e8 where action j is illegal (g2048_ppo_loss's convention):
+ *   pi = softmax(z), lp = log pi, ent = -sum_j lp_j pi_j
+ *   a* = the first maximum over j of teacher_q_j - (legal ? 0 : 1e8), in f32 (the engine's masked argmax)
+ *   p* = one-hot at a* for tau == 0; for tau > 0 p*_j = exp((q_j - q_a*) / tau) / sum over the legal j, 0 where illegal
+ *   ce = -sum over the legal j of p*_j lp_j, vl = (V - value_target)^2, el = -ent, tot = ce + c_value vl + c_entropy el
+ *   d tot / d z_j = (pi_j - p*_j) + c_entropy pi_j (lp_j + ent),  d tot / d V = 2 c_value (V - value_target)
+ * A sample without a legal action (mask_bits == 0) is all zeros - losses, agreement, new_logp and gradients - but counts in M. */
+
+/* The f32 elements of workspace that g2048_distill_loss needs, 5 per 256 samples; -1 for M < 1 or M > G2048_PPO_LOSS_MAX_BATCH. */
+int64_t g2048_distill_loss_workspace_floats(int64_t M);
+
+/* logits [M][4] and values [M]: f32, or bf16 when the *_bf16 flag is set; mask_bits u8 [M] (bit a = action a legal) or NULL for
+ * no masking; teacher_q f32 [M][4]; value_target f32 [M].  values, value_target and dvalues are NULL together: no critic term,
+ * sums[1] = 0 and dvalues is not touched.
+ * Out: new_logp f32 [M] = lp[a*]; sums f32 [5] = mean ce, mean vl, mean el, mean tot, mean agreement (1 where the first maximum
+ * of z is a*); dlogits [M][4] and dvalues [M] = d(mean tot)/d(input) in the input's dtype, multiplied by grad_scale (optional
+ * device f32 scalar) as in g2048_ppo_loss; running (optional device f64 [5]): running[k] += (double)sums[k].
+ * Two launches: one sample per lane in ceil(M / 256) workgroups whose five partial sums go to workspace, then one workgroup that
+ * adds them in ascending workgroup order.  No floating-point atomics: the same inputs give the same bits on any device.
+ * G2048_EINVAL, before any device work: a null logits, teacher_q, new_logp, sums, dlogits or workspace; values, value_target
+ * and dvalues not all null or all given; M for which g2048_distill_loss_workspace_floats returns -1; tau negative or not finite;
+ * teacher_q not 16-byte aligned, running not 8-byte aligned, a bf16 array not 2-byte or any other array not 4-byte aligned. */
+int g2048_distill_loss(const void *logits, int logits_bf16, const void *values, int values_bf16, const uint8_t *mask_bits,
+                       const float *teacher_q, const float *value_target, int64_t M, float tau, float c_value, float c_entropy,
+                       float *new_logp, float *sums, void *dlogits, void *dvalues, const float *grad_scale, double *running,
+                       float *workspace, void *stream);
+
+/* Row i of the minibatch = row idx[i] (int64, clamped to [0, N)) of the imitation ring: boards u8 [N][16], masks u8 [N],
+ * teacher_q f32 [N][4], value_target f32 [N] (NULL together with o_vt) -> the o_* arrays of M rows.  One launch; a board moves as
+ * one 16-byte word and the four scores as another.
+ * G2048_EINVAL: a null pointer other than that pair, value_target and o_vt not both null or both given, M < 1, N < 1, boards,
+ * o_boards, teacher_q or o_q not 16-byte aligned, idx not 8-byte aligned, value_target or o_vt not 4-byte aligned. */
+int g2048_distill_gather(const int64_t *idx, int64_t M, int64_t N, const uint8_t *boards, const uint8_t *masks, const float *teacher_q,
+                         const float *value_target, uint8_t *o_boards, uint8_t *o_masks, float *o_q, float *o_vt, void *stream);
+
 /* ---- policy network (update): feed-forward activation ---------------------------------------------------- */
 
 /* y = dropout(relu(x)), x and y bf16 [T][F] (F a multiple of 8, F <= 2048): `dropout(activation(linear1(x)))` of the
