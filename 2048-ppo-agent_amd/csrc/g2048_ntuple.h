@@ -5,6 +5,20 @@
 //   S(board)   = sum over g < 8, t < m of weights[t][idx(view_g(board), t)]          (int64)
 //   V(board)   = (float)S * 2^-F                                     (one int64 -> f32 conversion, one exact multiply)
 //
+// Multi-stage network (include/g2048.h, "multi-stage n-tuple network"): one [m][16^L] set of tables per stage of the game,
+//
+//   stage(x)     = #{ i : max over the 16 cells of x[c] >= k_i }     (the UNCLAMPED log2 tile against the n ascending thresholds)
+//   off(x, g, t) = ((stage(x) * m + t) << 4 L) + idx(view_g(x), t)   (the position in the flat [S][m][16^L] arrays, S = n + 1)
+//
+// The stage is that of the board being looked up: the afterstate in nt_score (a merge that creates tile k_i is valued by stage
+// i's tables), each leaf's afterstate in expectimax, prev_after in the learners.  The maximum is invariant under the eight
+// views, so it is computed once per board.  With S <= 8, m <= 8 and L <= 6 an offset is below 2^30: the u32 offsets stay.  Every
+// table access of the three kernel files goes through nt_offsets, so the stage enters there and nowhere else.  The thresholds
+// travel in NtNet; their count is wave-uniform and nt_offsets branches on it: a network without thresholds (all-zero, what a
+// memset leaves) is the single-stage network and skips the max-tile computation.  The kernels carry a template flag on top
+// (nt_kernel_net<STAGED>): launched with STAGED = false the count is a compile-time 0, the branch and everything behind it fold
+// away, and the single-stage kernels do no stage work at all.  The lane code itself needs no flag.
+//
 // The number of tuples M is a template parameter (1 .. 8): the 8 M table offsets of a lane are register arrays with
 // constant indices, so all 8 M gathers are in flight before the first is used.  The cells per tuple L stay a run-time
 // value (a wave-uniform trip count).  Built on g2048_device.h and g2048_symmetry.h only; every f32 operation is one
@@ -16,13 +30,60 @@
 
 namespace g2048 {
 
-enum { NT_MAX_TUPLES = 8, NT_MAX_CELLS = 6, NT_MAX_FRAC_BITS = 20 };
+enum { NT_MAX_TUPLES = 8, NT_MAX_CELLS = 6, NT_MAX_FRAC_BITS = 20, NT_MAX_STAGES = 8, NT_MAX_STAGE_TILE = 17 };
 
-// the network's shape: travels in the kernarg (wave-uniform -> SGPRs)
+// the network's shape: travels in the kernarg (wave-uniform -> SGPRs).  All-zero stage fields: a single stage.
 struct NtNet {
     uint8_t cell[NT_MAX_TUPLES][NT_MAX_CELLS];
     int L;
+    uint8_t stage_tile[NT_MAX_STAGES];  // the first n_stage_tiles are k_1 < k_2 < ...; the rest stay 0
+    int n_stage_tiles;                  // 0 .. NT_MAX_STAGES - 1 thresholds: n_stage_tiles + 1 stages
 };
+
+// the network as a kernel instance sees it: STAGED = false pins the threshold count to a compile-time 0
+template <bool STAGED>
+G_DEV NtNet nt_kernel_net(NtNet net) {
+    if (!STAGED) net.n_stage_tiles = 0;
+    return net;
+}
+
+// ---- the entry points' readers of the network (host code, one definition for the three .hip files) ----------------------------
+// the shape, checked and copied into the kernarg struct: m in 1 .. 8, L in 1 .. 6, cells < 16, distinct in a tuple.  Clears net.
+inline bool nt_read_net(const uint8_t *tuple_cells, int m, int L, NtNet &net) {
+    if (!tuple_cells || m < 1 || m > NT_MAX_TUPLES || L < 1 || L > NT_MAX_CELLS) return false;
+    memset(&net, 0, sizeof(net));
+    net.L = L;
+    for (int t = 0; t < m; ++t) {
+        unsigned seen = 0;
+        for (int j = 0; j < L; ++j) {
+            const uint8_t c = tuple_cells[t * L + j];
+            if (c > 15 || ((seen >> c) & 1u)) return false;
+            seen |= 1u << c;
+            net.cell[t][j] = c;
+        }
+    }
+    return true;
+}
+
+// the stages, after nt_read_net: n_stages in 1 .. 8 with n_stages - 1 thresholds in 1 .. 17, strictly ascending.  One stage takes
+// no thresholds (stage_tiles may be null and is not read).
+inline bool nt_read_stages(const uint8_t *stage_tiles, int n_stages, NtNet &net) {
+    if (n_stages < 1 || n_stages > NT_MAX_STAGES || (n_stages > 1 && !stage_tiles)) return false;
+    for (int i = 0; i + 1 < n_stages; ++i) {
+        const uint8_t k = stage_tiles[i];
+        if (k < 1 || k > NT_MAX_STAGE_TILE || (i > 0 && k <= stage_tiles[i - 1])) return false;
+        net.stage_tile[i] = k;
+    }
+    net.n_stage_tiles = n_stages - 1;
+    return true;
+}
+
+// what every staged entry point asks of its network arguments
+inline bool nt_read_staged(const uint8_t *tuple_cells, int m, int L, const uint8_t *stage_tiles, int n_stages, NtNet &net) {
+    return nt_read_net(tuple_cells, m, L, net) && nt_read_stages(stage_tiles, n_stages, net);
+}
+
+inline bool nt_frac_ok(int frac_bits) { return frac_bits >= 0 && frac_bits <= NT_MAX_FRAC_BITS; }
 
 // ---- memory operations: the compiler's global atomics on the device, plain accesses in the sequential host build -------------
 G_DEV void nt_add_i64(int64_t *p, int64_t v) {
@@ -76,14 +137,45 @@ G_DEV u32 nt_index(const NtNet &net, int t, const Board &bd) {
     return idx;
 }
 
-// off[g M + t] = t 16^L + idx(view_g(bd), t): the entry's position in the flat [m][16^L] arrays (< 2^27)
+// ---- stage --------------------------------------------------------------------------------------------------------------
+// the byte-wise maximum of two words whose bytes are below 128 (log2 tiles are at most 17): SWAR, no cell loop.  (a | 0x80) - b
+// never borrows across bytes and keeps bit 7 of a byte exactly where a >= b.
+G_DEV u32 nt_max_bytes(u32 a, u32 b) {
+    const u32 ge = ((a | 0x80808080u) - b) & 0x80808080u;
+    const u32 mask = ge | (ge - (ge >> 7));  // 0xFF in the bytes where a >= b
+    return b ^ ((a ^ b) & mask);
+}
+
+// the largest log2 tile of the board, unclamped: three byte-wise maxima over the four row words, two folds of the last word
+G_DEV u32 nt_max_tile(const Board &bd) {
+    u32 x = nt_max_bytes(nt_max_bytes(bd.r[0], bd.r[1]), nt_max_bytes(bd.r[2], bd.r[3]));
+    x = nt_max_bytes(x, x >> 16);
+    x = nt_max_bytes(x & 0xFFFFu, (x >> 8) & 0xFFu);
+    return x & 0xFFu;
+}
+
+// stage(bd) = the number of thresholds at or below the largest tile: 0 .. n_stage_tiles, whatever the bytes of bd are (so an
+// offset never leaves the [n_stage_tiles + 1][m][16^L] arrays).  The trip count is wave-uniform.
+G_DEV u32 nt_stage(const NtNet &net, const Board &bd) {
+    const u32 mx = nt_max_tile(bd);
+    u32 s = 0;
+#pragma unroll
+    for (int i = 0; i < NT_MAX_STAGES - 1; ++i)
+        if (i < net.n_stage_tiles) s += mx >= (u32)net.stage_tile[i] ? 1u : 0u;
+    return s;
+}
+
+// off[g M + t] = (stage(bd) M + t) 16^L + idx(view_g(bd), t): the entry's position in the flat [S][m][16^L] arrays (< 2^30).
+// The single-stage network (no thresholds) takes the scalar branch around the max-tile computation: base 0, the old offset.
 template <int M>
 G_DEV void nt_offsets(const NtNet &net, const Board &bd, u32 off[8 * M]) {
+    u32 base = 0;
+    if (net.n_stage_tiles) base = nt_stage(net, bd) * (u32)M;
 #pragma unroll
     for (u32 g = 0; g < 8; ++g) {
         const Board v = sym_view(bd, g);
 #pragma unroll
-        for (int t = 0; t < M; ++t) off[g * M + t] = ((u32)t << (4 * net.L)) + nt_index(net, t, v);
+        for (int t = 0; t < M; ++t) off[g * M + t] = ((base + (u32)t) << (4 * net.L)) + nt_index(net, t, v);
     }
 }
 

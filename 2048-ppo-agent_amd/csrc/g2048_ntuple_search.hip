@@ -46,9 +46,11 @@ __device__ __forceinline__ float quad_best(float q, bool legal) {
     return x == nt_neg_inf() ? 0.0f : x;
 }
 
-template <int M>
-__global__ void __launch_bounds__(kBlock) k_nt_q1(const uint8_t *boards, int plies, const int32_t *weights, const NtNet net,
+// STAGED = false: the threshold count is a compile-time 0 and no stage work is left (g2048_ntuple.h, nt_kernel_net)
+template <int M, bool STAGED>
+__global__ void __launch_bounds__(kBlock) k_nt_q1(const uint8_t *boards, int plies, const int32_t *weights, const NtNet net_arg,
                                                   float scale, float gamma, float *workspace, float *scores, float *values) {
+    const NtNet net = nt_kernel_net<STAGED>(net_arg);
     __shared__ __align__(8) float leaf[NTS_SLOTS];
     const u32 tid = threadIdx.x;
     int64_t b = blockIdx.x;
@@ -101,38 +103,25 @@ __global__ void __launch_bounds__(kBlock) k_nt_backup(const uint8_t *boards, int
 inline bool aligned4(const void *p) { return !((uintptr_t)p & 3); }
 inline bool aligned8(const void *p) { return !((uintptr_t)p & 7); }
 
-// the shape of the network, checked and copied into the kernarg struct as g2048_ntuple.hip does: m in 1 .. 8, L in 1 .. 6, cells
-// < 16, distinct in a tuple
-bool read_net(const uint8_t *tuple_cells, int m, int L, NtNet &net) {
-    if (!tuple_cells || m < 1 || m > NT_MAX_TUPLES || L < 1 || L > NT_MAX_CELLS) return false;
-    memset(&net, 0, sizeof(net));
-    net.L = L;
-    for (int t = 0; t < m; ++t) {
-        unsigned seen = 0;
-        for (int j = 0; j < L; ++j) {
-            const uint8_t c = tuple_cells[t * L + j];
-            if (c > 15 || ((seen >> c) & 1u)) return false;
-            seen |= 1u << c;
-            net.cell[t][j] = c;
-        }
-    }
-    return true;
-}
-
-inline bool frac_ok(int frac_bits) { return frac_bits >= 0 && frac_bits <= NT_MAX_FRAC_BITS; }
-
 }  // namespace
 
-#define G2048_NTS_LAUNCH(KERNEL, m, grid, stream, ...)                                                              \
-    switch (m) {                                                                                                    \
-        case 1: hipLaunchKernelGGL((KERNEL<1>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-        case 2: hipLaunchKernelGGL((KERNEL<2>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-        case 3: hipLaunchKernelGGL((KERNEL<3>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-        case 4: hipLaunchKernelGGL((KERNEL<4>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-        case 5: hipLaunchKernelGGL((KERNEL<5>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-        case 6: hipLaunchKernelGGL((KERNEL<6>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-        case 7: hipLaunchKernelGGL((KERNEL<7>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-        default: hipLaunchKernelGGL((KERNEL<8>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+#define G2048_NTS_LAUNCH_M(KERNEL, STAGED, m, grid, stream, ...) \
+    switch (m) { \
+        case 1: hipLaunchKernelGGL((KERNEL<1, STAGED>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+        case 2: hipLaunchKernelGGL((KERNEL<2, STAGED>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+        case 3: hipLaunchKernelGGL((KERNEL<3, STAGED>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+        case 4: hipLaunchKernelGGL((KERNEL<4, STAGED>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+        case 5: hipLaunchKernelGGL((KERNEL<5, STAGED>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+        case 6: hipLaunchKernelGGL((KERNEL<6, STAGED>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+        case 7: hipLaunchKernelGGL((KERNEL<7, STAGED>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+        default: hipLaunchKernelGGL((KERNEL<8, STAGED>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+    }
+// `net` is the network the entry point has just read: a single stage launches the kernels without stage work
+#define G2048_NTS_LAUNCH(KERNEL, m, grid, stream, ...) \
+    if (net.n_stage_tiles) { \
+        G2048_NTS_LAUNCH_M(KERNEL, true, m, grid, stream, __VA_ARGS__) \
+    } else { \
+        G2048_NTS_LAUNCH_M(KERNEL, false, m, grid, stream, __VA_ARGS__) \
     }
 
 extern "C" {
@@ -143,11 +132,13 @@ int64_t g2048_ntuple_expectimax_workspace_floats(int64_t B, int plies) {
     return -1;
 }
 
-int g2048_ntuple_expectimax(const uint8_t *boards, int64_t B, const int32_t *weights, const uint8_t *tuple_cells, int m, int L,
-                            int frac_bits, int plies, double gamma, float *workspace, float *scores, float *values, void *stream) {
+int g2048_ntuple_staged_expectimax(const uint8_t *boards, int64_t B, const int32_t *weights, const uint8_t *tuple_cells, int m, int L,
+                                   const uint8_t *stage_tiles, int n_stages, int frac_bits, int plies, double gamma, float *workspace,
+                                   float *scores, float *values, void *stream) {
     NtNet net;
     if (!boards || !weights || !scores || !values || g2048_ntuple_expectimax_workspace_floats(B, plies) < 0 ||
-        (plies == 2 && !workspace) || !read_net(tuple_cells, m, L, net) || !frac_ok(frac_bits) || !(gamma >= 0.0) || !isfinite(gamma))
+        (plies == 2 && !workspace) || !nt_read_staged(tuple_cells, m, L, stage_tiles, n_stages, net) || !nt_frac_ok(frac_bits) ||
+        !(gamma >= 0.0) || !isfinite(gamma))
         return G2048_EINVAL;
     if (!aligned16(boards) || !aligned4(weights) || !aligned4(scores) || !aligned4(values) || !aligned8(workspace)) return G2048_EINVAL;
     const unsigned grid = (unsigned)(plies == 1 ? B : NTS_SLOTS * B);
@@ -157,6 +148,13 @@ int g2048_ntuple_expectimax(const uint8_t *boards, int64_t B, const int32_t *wei
         hipLaunchKernelGGL(k_nt_backup, dim3((unsigned)((4 * B + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, boards, B,
                            workspace, (float)gamma, scores, values);
     return launch_status();
+}
+
+// the unstaged entry point: one stage, no thresholds
+int g2048_ntuple_expectimax(const uint8_t *boards, int64_t B, const int32_t *weights, const uint8_t *tuple_cells, int m, int L,
+                            int frac_bits, int plies, double gamma, float *workspace, float *scores, float *values, void *stream) {
+    return g2048_ntuple_staged_expectimax(boards, B, weights, tuple_cells, m, L, nullptr, 1, frac_bits, plies, gamma, workspace, scores,
+                                          values, stream);
 }
 
 }  // extern "C"

@@ -12,6 +12,10 @@ protocol of ``evaluate_max_tile`` (``--eval-episodes`` episodes, seed 42, batche
 ``--eval-plies 0 1 2`` plays every evaluation point once per listed expectimax depth over the network (0: greedy, the default).
 ``--learner tc`` learns by temporal coherence (a step size per table entry, ``NTupleTrainer``); it is meant to run at ``--alpha 1.0``
 and records the coherence numbers (entries with a rate, their mean rate) at every evaluation point.
+``--stage-tiles 11 12 13 14`` trains a multi-stage network (one set of tables per max-tile stage, ``NTupleNetwork``); the trainer
+splits a stage off at the first check, every ``--promote-every`` lock-steps, at which a training board has reached its threshold.
+The result records ``stage_tiles``, every promotion (lock-step, training seconds at the end of its chunk) and ``active_stages`` at
+every evaluation point.
 """
 import argparse
 import json
@@ -39,6 +43,9 @@ def main():
     ap.add_argument("--eval-episodes", type=int, default=1000)
     ap.add_argument("--eval-plies", type=int, nargs="+", default=[0], choices=(0, 1, 2),
                     help="expectimax depths to evaluate at: every evaluation point plays the same seeds once per depth")
+    ap.add_argument("--stage-tiles", type=int, nargs="+", default=None, metavar="K",
+                    help="log2 tile thresholds of a multi-stage network, ascending (11 12 13 14: a stage from 2048, 4096, 8192, 16384)")
+    ap.add_argument("--promote-every", type=int, default=64, metavar="N", help="lock-steps between two promotion checks (0: never)")
     ap.add_argument("--chunk", type=int, default=50, help="lock-steps between two looks at the clock")
     ap.add_argument("--seed", type=int, default=0, help="seed of the training environments")
     ap.add_argument("--out", default=None, help="write the JSON result here")
@@ -47,12 +54,14 @@ def main():
 
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    net = NTupleNetwork(device=dev)
-    trainer = NTupleTrainer(net, args.envs, alpha=args.alpha, seed=args.seed, device=dev, learner=args.learner)
+    net = NTupleNetwork(device=dev, stage_tiles=args.stage_tiles)
+    trainer = NTupleTrainer(net, args.envs, alpha=args.alpha, seed=args.seed, device=dev, learner=args.learner,
+                            promote_every=args.promote_every)
     budget = args.minutes * 60.0
     points = sorted(60.0 * m for m in args.eval_at) if args.eval_at else [budget * (k + 1) / args.evals for k in range(max(args.evals, 1))]
     result = dict(envs=args.envs, learner=args.learner, alpha=args.alpha, seed=args.seed, tuples=[list(t) for t in net.tuples],
-                  frac_bits=net.frac_bits, minutes=args.minutes, first_2048=None, evaluations=[])
+                  frac_bits=net.frac_bits, minutes=args.minutes, first_2048=None, evaluations=[],
+                  stage_tiles=None if net.stage_tiles is None else list(net.stage_tiles), promote_every=args.promote_every, promotions=[])
     trained = 0.0
     episodes = 0
     while points:
@@ -61,6 +70,9 @@ def main():
         top = int(trainer.boards.max().item())  # the one host read of a chunk (it also ends the chunk's clock)
         trained += time.perf_counter() - t0
         episodes += int(out["episodes"].item())
+        for lock_step, active in trainer.promotions[len(result["promotions"]):]:  # those of this chunk, timed at its end
+            result["promotions"].append(dict(lock_step=lock_step, active_stages=active, train_seconds=round(trained, 2)))
+            print(f"stage {active - 1} split off at lock-step {lock_step} ({trained:.1f} s of training)", flush=True)
         if result["first_2048"] is None and top >= 11:
             result["first_2048"] = dict(seconds=round(trained, 2), lock_steps=trainer.lock_steps)
             print(f"first 2048 tile on a training board after {trained:.1f} s, {trainer.lock_steps} lock-steps", flush=True)
@@ -74,7 +86,7 @@ def main():
             for plies in args.eval_plies:
                 ev = evaluate_ntuple(net, dev, num_episodes=args.eval_episodes, seed=42, plies=plies)
                 ev.update(plies=plies, train_seconds=round(trained, 2), lock_steps=trainer.lock_steps, episodes_trained=episodes,
-                          max_abs_weight=int(net.weights.abs().max().item()))
+                          max_abs_weight=int(net.weights.abs().max().item()), active_stages=net.active_stages)
                 if coherence is not None:
                     ev.update(coherence=coherence)
                 result["evaluations"].append(ev)

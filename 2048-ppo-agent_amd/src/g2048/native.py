@@ -458,23 +458,46 @@ def _tuple_cells(tuple_cells):
     return cells, cells.shape[0], cells.shape[1]
 
 
-def ntuple_values(boards, weights, tuple_cells, frac_bits: int, values):
-    """values f32 [n] = V(boards u8 [n,16]) of the n-tuple network ``weights`` i32 [m, 16^L] over ``tuple_cells`` u8 [m, L] (host)."""
+def _stages(stage_tiles):
+    """stage_tiles, the ascending log2 tile thresholds (host) -> (contiguous u8 array, n_stages = their number + 1)."""
+    st = np.ascontiguousarray(stage_tiles, np.uint8)
+    if st.ndim != 1:
+        raise NativeError(f"stage_tiles: expected a flat sequence of log2 tile values, got shape {st.shape}")
+    return st, st.size + 1
+
+
+def ntuple_values(boards, weights, tuple_cells, frac_bits: int, values, stage_tiles=None):
+    """values f32 [n] = V(boards u8 [n,16]) of the n-tuple network ``weights`` i32 [m, 16^L] over ``tuple_cells`` u8 [m, L] (host).
+    ``stage_tiles`` (here and below): None, or the thresholds of a multi-stage network (host), whose tables are [S, m, 16^L]."""
     cells, m, L = _tuple_cells(tuple_cells)
     n = values.numel()
-    _check(load().g2048_ntuple_values(_dev(boards, u8, 16 * n, "boards"), n, _dev(weights, i32, m * 16 ** L, "weights"),
-                                      cells.ctypes.data, m, L, int(frac_bits), _dev(values, f32, n, "values"), _stream()),
-           "g2048_ntuple_values")
+    if stage_tiles is None:
+        _check(load().g2048_ntuple_values(_dev(boards, u8, 16 * n, "boards"), n, _dev(weights, i32, m * 16 ** L, "weights"),
+                                          cells.ctypes.data, m, L, int(frac_bits), _dev(values, f32, n, "values"), _stream()),
+               "g2048_ntuple_values")
+        return
+    st, S = _stages(stage_tiles)
+    _check(load().g2048_ntuple_staged_values(_dev(boards, u8, 16 * n, "boards"), n, _dev(weights, i32, S * m * 16 ** L, "weights"),
+                                             cells.ctypes.data, m, L, st.ctypes.data, S, int(frac_bits),
+                                             _dev(values, f32, n, "values"), _stream()),
+           "g2048_ntuple_staged_values")
 
 
-def ntuple_scores(boards, weights, tuple_cells, frac_bits: int, scores, values):
+def ntuple_scores(boards, weights, tuple_cells, frac_bits: int, scores, values, stage_tiles=None):
     """scores f32 [B,4] = reward + V(afterstate) per action (+0 where illegal), values f32 [B] = the max over the legal ones."""
     cells, m, L = _tuple_cells(tuple_cells)
     B = values.numel()
-    _check(load().g2048_ntuple_scores(_dev(boards, u8, 16 * B, "boards"), B, _dev(weights, i32, m * 16 ** L, "weights"),
-                                      cells.ctypes.data, m, L, int(frac_bits), _dev(scores, f32, 4 * B, "scores"),
-                                      _dev(values, f32, B, "values"), _stream()),
-           "g2048_ntuple_scores")
+    if stage_tiles is None:
+        _check(load().g2048_ntuple_scores(_dev(boards, u8, 16 * B, "boards"), B, _dev(weights, i32, m * 16 ** L, "weights"),
+                                          cells.ctypes.data, m, L, int(frac_bits), _dev(scores, f32, 4 * B, "scores"),
+                                          _dev(values, f32, B, "values"), _stream()),
+               "g2048_ntuple_scores")
+        return
+    st, S = _stages(stage_tiles)
+    _check(load().g2048_ntuple_staged_scores(_dev(boards, u8, 16 * B, "boards"), B, _dev(weights, i32, S * m * 16 ** L, "weights"),
+                                             cells.ctypes.data, m, L, st.ctypes.data, S, int(frac_bits),
+                                             _dev(scores, f32, 4 * B, "scores"), _dev(values, f32, B, "values"), _stream()),
+           "g2048_ntuple_staged_scores")
 
 
 def ntuple_expectimax_workspace_floats(B: int, plies: int) -> int:
@@ -485,65 +508,115 @@ def ntuple_expectimax_workspace_floats(B: int, plies: int) -> int:
     return n
 
 
-def ntuple_expectimax(boards, weights, tuple_cells, frac_bits: int, plies: int, gamma: float, workspace, scores, values):
+def ntuple_expectimax(boards, weights, tuple_cells, frac_bits: int, plies: int, gamma: float, workspace, scores, values,
+                      stage_tiles=None):
     """scores f32 [B,4] = the ``plies``-ply (1 or 2) expectimax Q over the n-tuple network's greedy value, values f32 [B] = the max
     over the legal moves.  workspace: f32 [>= 128 B] for two plies, None (or anything) for one; its contents do not matter."""
     cells, m, L = _tuple_cells(tuple_cells)
     B, plies = values.numel(), int(plies)
     need = ntuple_expectimax_workspace_floats(B, plies)
-    _check(load().g2048_ntuple_expectimax(_dev(boards, u8, 16 * B, "boards"), B, _dev(weights, i32, m * 16 ** L, "weights"),
-                                          cells.ctypes.data, m, L, int(frac_bits), plies, float(gamma),
-                                          _dev(workspace, f32, need, "workspace", optional=need == 0),
-                                          _dev(scores, f32, 4 * B, "scores"), _dev(values, f32, B, "values"), _stream()),
-           "g2048_ntuple_expectimax")
+    if stage_tiles is None:
+        _check(load().g2048_ntuple_expectimax(_dev(boards, u8, 16 * B, "boards"), B, _dev(weights, i32, m * 16 ** L, "weights"),
+                                              cells.ctypes.data, m, L, int(frac_bits), plies, float(gamma),
+                                              _dev(workspace, f32, need, "workspace", optional=need == 0),
+                                              _dev(scores, f32, 4 * B, "scores"), _dev(values, f32, B, "values"), _stream()),
+               "g2048_ntuple_expectimax")
+        return
+    st, S = _stages(stage_tiles)
+    _check(load().g2048_ntuple_staged_expectimax(_dev(boards, u8, 16 * B, "boards"), B,
+                                                 _dev(weights, i32, S * m * 16 ** L, "weights"), cells.ctypes.data, m, L,
+                                                 st.ctypes.data, S, int(frac_bits), plies, float(gamma),
+                                                 _dev(workspace, f32, need, "workspace", optional=need == 0),
+                                                 _dev(scores, f32, 4 * B, "scores"), _dev(values, f32, B, "values"), _stream()),
+           "g2048_ntuple_staged_expectimax")
 
 
-def ntuple_td_accumulate(prev_after, flag, target, weights, tuple_cells, frac_bits: int, alpha: float, acc, cnt, td_error=None):
+def ntuple_td_accumulate(prev_after, flag, target, weights, tuple_cells, frac_bits: int, alpha: float, acc, cnt, td_error=None,
+                         stage_tiles=None):
     """The accumulate half of one TD(0) lock-step: acc i64 [m, 16^L] += delta, cnt i32 [m, 16^L] += 1 at the entries of every env
     with flag != 0.  td_error f32 [B] or None."""
     cells, m, L = _tuple_cells(tuple_cells)
     B, E = flag.numel(), m * 16 ** L
-    _check(load().g2048_ntuple_td_accumulate(_dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"),
-                                             _dev(target, f32, B, "target"), B, _dev(weights, i32, E, "weights"), cells.ctypes.data,
-                                             m, L, int(frac_bits), float(alpha), _dev(acc, i64, E, "acc"), _dev(cnt, i32, E, "cnt"),
-                                             _dev(td_error, f32, B, "td_error", optional=True), _stream()),
-           "g2048_ntuple_td_accumulate")
+    if stage_tiles is None:
+        _check(load().g2048_ntuple_td_accumulate(_dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"),
+                                                 _dev(target, f32, B, "target"), B, _dev(weights, i32, E, "weights"),
+                                                 cells.ctypes.data, m, L, int(frac_bits), float(alpha), _dev(acc, i64, E, "acc"),
+                                                 _dev(cnt, i32, E, "cnt"), _dev(td_error, f32, B, "td_error", optional=True),
+                                                 _stream()),
+               "g2048_ntuple_td_accumulate")
+        return
+    st, S = _stages(stage_tiles)
+    E *= S
+    _check(load().g2048_ntuple_staged_td_accumulate(_dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"),
+                                                    _dev(target, f32, B, "target"), B, _dev(weights, i32, E, "weights"),
+                                                    cells.ctypes.data, m, L, st.ctypes.data, S, int(frac_bits), float(alpha),
+                                                    _dev(acc, i64, E, "acc"), _dev(cnt, i32, E, "cnt"),
+                                                    _dev(td_error, f32, B, "td_error", optional=True), _stream()),
+           "g2048_ntuple_staged_td_accumulate")
 
 
-def ntuple_td_apply(prev_after, flag, tuple_cells, weights, acc, cnt):
+def ntuple_td_apply(prev_after, flag, tuple_cells, weights, acc, cnt, stage_tiles=None):
     """The apply half: weights += the rounded mean acc / cnt at every entry the same boards hit, acc = cnt = 0 there."""
     cells, m, L = _tuple_cells(tuple_cells)
     B, E = flag.numel(), m * 16 ** L
-    _check(load().g2048_ntuple_td_apply(_dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"), B, cells.ctypes.data,
-                                        m, L, _dev(weights, i32, E, "weights"), _dev(acc, i64, E, "acc"), _dev(cnt, i32, E, "cnt"),
-                                        _stream()),
-           "g2048_ntuple_td_apply")
+    if stage_tiles is None:
+        _check(load().g2048_ntuple_td_apply(_dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"), B,
+                                            cells.ctypes.data, m, L, _dev(weights, i32, E, "weights"), _dev(acc, i64, E, "acc"),
+                                            _dev(cnt, i32, E, "cnt"), _stream()),
+               "g2048_ntuple_td_apply")
+        return
+    st, S = _stages(stage_tiles)
+    E *= S
+    _check(load().g2048_ntuple_staged_td_apply(_dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"), B,
+                                               cells.ctypes.data, m, L, st.ctypes.data, S, _dev(weights, i32, E, "weights"),
+                                               _dev(acc, i64, E, "acc"), _dev(cnt, i32, E, "cnt"), _stream()),
+           "g2048_ntuple_staged_td_apply")
 
 
 def ntuple_tc_accumulate(prev_after, flag, target, weights, tuple_cells, frac_bits: int, alpha: float, acc, abs_acc, cnt,
-                         td_error=None):
+                         td_error=None, stage_tiles=None):
     """The accumulate half of one TC lock-step: acc i64 [m, 16^L] += delta, abs_acc i64 [m, 16^L] += |delta|, cnt i32 [m, 16^L] += 1
     at the entries of every env with flag != 0.  td_error f32 [B] or None."""
     cells, m, L = _tuple_cells(tuple_cells)
     B, E = flag.numel(), m * 16 ** L
-    _check(load().g2048_ntuple_tc_accumulate(_dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"),
-                                             _dev(target, f32, B, "target"), B, _dev(weights, i32, E, "weights"), cells.ctypes.data,
-                                             m, L, int(frac_bits), float(alpha), _dev(acc, i64, E, "acc"),
-                                             _dev(abs_acc, i64, E, "abs_acc"), _dev(cnt, i32, E, "cnt"),
-                                             _dev(td_error, f32, B, "td_error", optional=True), _stream()),
-           "g2048_ntuple_tc_accumulate")
+    if stage_tiles is None:
+        _check(load().g2048_ntuple_tc_accumulate(_dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"),
+                                                 _dev(target, f32, B, "target"), B, _dev(weights, i32, E, "weights"),
+                                                 cells.ctypes.data, m, L, int(frac_bits), float(alpha), _dev(acc, i64, E, "acc"),
+                                                 _dev(abs_acc, i64, E, "abs_acc"), _dev(cnt, i32, E, "cnt"),
+                                                 _dev(td_error, f32, B, "td_error", optional=True), _stream()),
+               "g2048_ntuple_tc_accumulate")
+        return
+    st, S = _stages(stage_tiles)
+    E *= S
+    _check(load().g2048_ntuple_staged_tc_accumulate(_dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"),
+                                                    _dev(target, f32, B, "target"), B, _dev(weights, i32, E, "weights"),
+                                                    cells.ctypes.data, m, L, st.ctypes.data, S, int(frac_bits), float(alpha),
+                                                    _dev(acc, i64, E, "acc"), _dev(abs_acc, i64, E, "abs_acc"),
+                                                    _dev(cnt, i32, E, "cnt"), _dev(td_error, f32, B, "td_error", optional=True),
+                                                    _stream()),
+           "g2048_ntuple_staged_tc_accumulate")
 
 
-def ntuple_tc_apply(prev_after, flag, tuple_cells, weights, acc, abs_acc, cnt, coh_e, coh_a):
+def ntuple_tc_apply(prev_after, flag, tuple_cells, weights, acc, abs_acc, cnt, coh_e, coh_a, stage_tiles=None):
     """The apply half: every entry the same boards hit moves by its rounded mean delta times its rate |coh_e| / coh_a (rate 1
     where coh_a == 0), coh_e += the mean, coh_a += the mean magnitude, acc = abs_acc = cnt = 0 there."""
     cells, m, L = _tuple_cells(tuple_cells)
     B, E = flag.numel(), m * 16 ** L
-    _check(load().g2048_ntuple_tc_apply(_dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"), B, cells.ctypes.data,
-                                        m, L, _dev(weights, i32, E, "weights"), _dev(acc, i64, E, "acc"),
-                                        _dev(abs_acc, i64, E, "abs_acc"), _dev(cnt, i32, E, "cnt"), _dev(coh_e, i32, E, "coh_e"),
-                                        _dev(coh_a, i32, E, "coh_a"), _stream()),
-           "g2048_ntuple_tc_apply")
+    if stage_tiles is None:
+        _check(load().g2048_ntuple_tc_apply(_dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"), B,
+                                            cells.ctypes.data, m, L, _dev(weights, i32, E, "weights"), _dev(acc, i64, E, "acc"),
+                                            _dev(abs_acc, i64, E, "abs_acc"), _dev(cnt, i32, E, "cnt"), _dev(coh_e, i32, E, "coh_e"),
+                                            _dev(coh_a, i32, E, "coh_a"), _stream()),
+               "g2048_ntuple_tc_apply")
+        return
+    st, S = _stages(stage_tiles)
+    E *= S
+    _check(load().g2048_ntuple_staged_tc_apply(_dev(prev_after, u8, 16 * B, "prev_after"), _dev(flag, u8, B, "flag"), B,
+                                               cells.ctypes.data, m, L, st.ctypes.data, S, _dev(weights, i32, E, "weights"),
+                                               _dev(acc, i64, E, "acc"), _dev(abs_acc, i64, E, "abs_acc"), _dev(cnt, i32, E, "cnt"),
+                                               _dev(coh_e, i32, E, "coh_e"), _dev(coh_a, i32, E, "coh_a"), _stream()),
+           "g2048_ntuple_staged_tc_apply")
 
 
 def ntuple_link(tr_boards_row, tr_meta_row, prev_after, flag):

@@ -23,6 +23,7 @@ from .q_player import QPlayer
 
 DEFAULT_TUPLES = ((0, 1, 2, 3, 4, 5), (4, 5, 6, 7, 8, 9), (0, 1, 2, 4, 5, 6), (4, 5, 6, 8, 9, 10))
 MAX_TUPLES, MAX_CELLS, MAX_FRAC_BITS = 8, 6, 20
+MAX_STAGES, MAX_STAGE_TILE = 8, 17
 SEARCH_CHUNK = 1 << 16  # roots per two-ply call: 128 workspace floats each
 
 
@@ -59,6 +60,25 @@ def _check_tuples(tuples) -> np.ndarray:
     return np.ascontiguousarray(np.array(rows, np.uint8).reshape(len(rows), L))
 
 
+def _check_stage_tiles(stage_tiles):
+    """-> None (unstaged) or the thresholds as a tuple of ints: 1 .. 7 log2 tile values in 1 .. 17, strictly ascending."""
+    if stage_tiles is None:
+        return None
+    try:
+        tiles = tuple(stage_tiles)
+    except TypeError:
+        raise ValueError(f"stage_tiles must be a sequence of log2 tile values, got {stage_tiles!r}") from None
+    if not 1 <= len(tiles) <= MAX_STAGES - 1:
+        raise ValueError(f"stage_tiles holds 1 .. {MAX_STAGES - 1} thresholds, got {len(tiles)}")
+    for k in tiles:
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_STAGE_TILE:
+            raise ValueError(f"a stage threshold is an integer log2 tile value in 1 .. {MAX_STAGE_TILE}, got {k!r}")
+    tiles = tuple(int(k) for k in tiles)
+    if any(a >= b for a, b in zip(tiles, tiles[1:])):
+        raise ValueError(f"stage_tiles must be strictly ascending, got {tiles!r}")
+    return tiles
+
+
 def _device(device) -> torch.device:
     return C.device() if device is None else torch.device(device)
 
@@ -66,25 +86,75 @@ def _device(device) -> torch.device:
 class NTupleNetwork:
     """``weights`` i32 [m, 16^L] (zeros) over ``tuples``: m tuples (1 .. 8) of L distinct cells each (1 .. 6), fixed point with
     ``frac_bits`` fractional bits (0 .. 20; the default 12 resolves 2.4e-4 and holds +-524 288 per entry).  The default network,
-    four 6-tuples, is 256 MB.  Bad settings raise ``ValueError`` before any device is touched."""
+    four 6-tuples, is 256 MB.  Bad settings raise ``ValueError`` before any device is touched.
 
-    def __init__(self, tuples=DEFAULT_TUPLES, frac_bits: int = 12, device=None):
+    ``stage_tiles=(k_1 < ... < k_n)`` (log2 tile values in 1 .. 17, n in 1 .. 7) makes it a MULTI-STAGE network of ``stages`` = n + 1
+    sets of tables, ``weights`` i32 [S, m, 16^L]: a board is looked up in stage #{i : its largest tile >= k_i} (the afterstate's own
+    stage in ``scores``, each leaf's in ``expectimax``).  Stages are split off in order: ``active_stages`` = p (1 at the start) means
+    that the kernels see the first p - 1 thresholds only, so boards at or above k_p are served, and learned, by stage p - 1's tables
+    until ``promote()`` copies them into stage p (``weights[p] = weights[p - 1]``, ``active_stages = p + 1``): right after it every
+    value, score and search result is what it was before, bit for bit.  Memory is S times the unstaged network's: the default
+    tuples with ``stage_tiles=(11, 12, 13, 14)`` hold 1.34 GB of weights.  ``stage_tiles=None`` is the unstaged network, unchanged."""
+
+    def __init__(self, tuples=DEFAULT_TUPLES, frac_bits: int = 12, device=None, stage_tiles=None):
         self.cells = _check_tuples(tuples)
+        self.stage_tiles = _check_stage_tiles(stage_tiles)
+        self.stages = 1 if self.stage_tiles is None else len(self.stage_tiles) + 1
+        self._active = 1
         if not 0 <= int(frac_bits) <= MAX_FRAC_BITS:
             raise ValueError(f"frac_bits must be in 0 .. {MAX_FRAC_BITS}, got {frac_bits!r}")
         self.frac_bits = int(frac_bits)
         self.tuples = tuple(tuple(int(c) for c in t) for t in self.cells)
         self.m, self.L = self.cells.shape
         self.device = _device(device)
-        self.weights = torch.zeros((self.m, 16 ** self.L), dtype=torch.int32, device=self.device)
+        shape = (self.m, 16 ** self.L) if self.stage_tiles is None else (self.stages, self.m, 16 ** self.L)
+        self.weights = torch.zeros(shape, dtype=torch.int32, device=self.device)
         self._search_ws = None  # the two-ply workspace, allocated at the first two-ply call
+
+    @property
+    def active_stages(self) -> int:
+        """p in 1 .. ``stages``: the stages split off so far (always 1 for the unstaged network)."""
+        return self._active
+
+    @active_stages.setter
+    def active_stages(self, p) -> None:
+        if isinstance(p, bool) or not isinstance(p, (int, np.integer)) or not 1 <= int(p) <= self.stages:
+            raise ValueError(f"active_stages must be an integer in 1 .. {self.stages}, got {p!r}")
+        self._active = int(p)
+
+    @property
+    def active_tiles(self):
+        """What the kernels are given: None for the unstaged network, else the first ``active_stages - 1`` thresholds (u8, host)."""
+        if self.stage_tiles is None:
+            return None
+        return np.array(self.stage_tiles[:self._active - 1], np.uint8)
+
+    def promote(self) -> int:
+        """Split the next stage off: ``weights[p] = weights[p - 1]``, ``active_stages = p + 1`` -> the new ``active_stages``.
+        ``ValueError`` at the top stage (and for the unstaged network, whose one stage is its top)."""
+        p = self._active
+        if p >= self.stages:
+            raise ValueError(f"all {self.stages} stages are active: nothing to promote")
+        self.weights[p].copy_(self.weights[p - 1])
+        self._active = p + 1
+        return self._active
+
+    def stage_of(self, boards: torch.Tensor) -> torch.Tensor:
+        """boards u8 [n, 16] -> u8 [n]: the stage whose tables a board is looked up in now (over the ACTIVE thresholds; plain torch,
+        for logging)."""
+        mx = boards.reshape(-1, 16).max(dim=1).values
+        tiles = [] if self.stage_tiles is None else self.stage_tiles[:self._active - 1]
+        out = torch.zeros(mx.shape, dtype=torch.uint8, device=boards.device)
+        for k in tiles:
+            out += (mx >= k).to(torch.uint8)
+        return out
 
     def values(self, boards: torch.Tensor) -> torch.Tensor:
         """boards u8 [n, 16] -> V f32 [n]."""
         boards = boards.contiguous()
         out = torch.empty(boards.shape[0], dtype=torch.float32, device=boards.device)
         if out.numel():
-            nv.ntuple_values(boards, self.weights, self.cells, self.frac_bits, out)
+            nv.ntuple_values(boards, self.weights, self.cells, self.frac_bits, out, self.active_tiles)
         return out
 
     def scores(self, boards: torch.Tensor):
@@ -95,7 +165,7 @@ class NTupleNetwork:
         q = torch.empty((B, 4), dtype=torch.float32, device=boards.device)
         v = torch.empty(B, dtype=torch.float32, device=boards.device)
         if B:
-            nv.ntuple_scores(boards, self.weights, self.cells, self.frac_bits, q, v)
+            nv.ntuple_scores(boards, self.weights, self.cells, self.frac_bits, q, v, self.active_tiles)
         return q, v
 
     def expectimax(self, boards: torch.Tensor, plies: int, gamma: float = 1.0):
@@ -117,18 +187,23 @@ class NTupleNetwork:
         step = SEARCH_CHUNK if plies == 2 else 1 << 24  # the entry point's own limit for one ply
         for s in range(0, B, step):
             e = min(B, s + step)
-            nv.ntuple_expectimax(boards[s:e], self.weights, self.cells, self.frac_bits, plies, gamma, ws, q[s:e], v[s:e])
+            nv.ntuple_expectimax(boards[s:e], self.weights, self.cells, self.frac_bits, plies, gamma, ws, q[s:e], v[s:e],
+                                 self.active_tiles)
         return q, v
 
     def save(self, path: str) -> None:
-        torch.save({"weights": self.weights.cpu(), "tuples": self.tuples, "frac_bits": self.frac_bits}, path)
+        torch.save({"weights": self.weights.cpu(), "tuples": self.tuples, "frac_bits": self.frac_bits,
+                    "stage_tiles": self.stage_tiles, "active_stages": self._active}, path)
 
     @classmethod
     def load(cls, path: str, device=None) -> "NTupleNetwork":
+        """A file written before the network had stages (no ``stage_tiles`` key) loads as an unstaged network."""
         d = torch.load(path, map_location="cpu")
-        net = cls(d["tuples"], d["frac_bits"], device=device)
+        net = cls(d["tuples"], d["frac_bits"], device=device, stage_tiles=d.get("stage_tiles"))
         if tuple(d["weights"].shape) != tuple(net.weights.shape) or d["weights"].dtype != torch.int32:
-            raise ValueError(f"{path}: weights of shape {tuple(d['weights'].shape)} do not fit tuples {net.tuples}")
+            raise ValueError(f"{path}: weights of shape {tuple(d['weights'].shape)} do not fit tuples {net.tuples} "
+                             f"and stage_tiles {net.stage_tiles}")
+        net.active_stages = d.get("active_stages", 1)
         net.weights.copy_(d["weights"])
         return net
 
@@ -180,14 +255,25 @@ class NTupleTrainer:
     (i64), ``coh_e`` and ``coh_a`` (i32) to ``acc`` and ``cnt``: at the default network the trainer then holds about 2.3 GB of tables
     (weights 0.27, acc and abs_acc 0.54 each, cnt, coh_e and coh_a 0.27 each) where ``"td0"`` holds 1.07 GB.  Anything but ``"td0"``
     or ``"tc"`` raises ``ValueError`` before a device is touched.
+
+    On a multi-stage network every learner table takes the weights' shape [S, m, 16^L], so the table memory is S times the figures
+    above, per stage 1.07 GB for ``"td0"`` and 2.3 GB for ``"tc"`` at the default tuples: about 11.5 GB for TC at S = 5.  The
+    kernels get the network's active thresholds, and the trainer promotes: before a lock-step whose global count (``lock_steps``)
+    is a positive multiple of ``promote_every`` it reads ``prev_after.max()`` (one torch reduction and one host read, the only one
+    the loop has, and only while a stage is left to split off) and calls ``network.promote()`` while that maximum is at or above
+    the next threshold, several times at one check if need be.  ``promote_every=0`` never promotes.  A new stage's ``coh_e`` /
+    ``coh_a`` stay zero (rate 1).  ``promotions`` lists ``(lock_steps, new active_stages)``.  The count is global, so
+    ``train(48)`` and ``train(20); train(28)`` give the same bits.
     """
 
     LEARNERS = ("td0", "tc")
 
     def __init__(self, network: NTupleNetwork, num_envs: int, alpha: float = 0.1, seed: int = 0, rng_mode=None, device=None,
-                 learner: str = "td0"):
+                 learner: str = "td0", promote_every: int = 64):
         if learner not in self.LEARNERS:
             raise ValueError(f"learner must be one of {self.LEARNERS}, got {learner!r}")
+        if isinstance(promote_every, bool) or not isinstance(promote_every, (int, np.integer)) or promote_every < 0:
+            raise ValueError(f"promote_every must be a non-negative integer (0: never promote), got {promote_every!r}")
         if not isinstance(network, NTupleNetwork):
             raise ValueError(f"network must be an NTupleNetwork, got {type(network).__name__}")
         if int(num_envs) < 1:
@@ -225,6 +311,17 @@ class NTupleTrainer:
                         values=torch.empty((1, B), dtype=f32, device=dev))
         self._started = False
         self.lock_steps = 0
+        self.promote_every = int(promote_every)
+        self.promotions = []
+
+    def _promote_if_reached(self, count: int) -> None:
+        """The promotion check in front of lock-step ``count`` (see the class docstring)."""
+        net = self.network
+        if not self.promote_every or count == 0 or count % self.promote_every or net.active_stages >= net.stages:
+            return
+        top = int(self.prev_after.max().item())
+        while net.active_stages < net.stages and top >= net.stage_tiles[net.active_stages - 1]:
+            self.promotions.append((count, net.promote()))
 
     @torch.no_grad()
     def train(self, lock_steps: int, record: bool = False):
@@ -248,16 +345,18 @@ class NTupleTrainer:
                        scores=torch.empty((T, B, 4), dtype=torch.float32, device=self.device),
                        targets=torch.empty((T, B), dtype=torch.float32, device=self.device))
         for t in range(T):
-            nv.ntuple_scores(self.boards, net.weights, net.cells, net.frac_bits, self.scores, self.targets)
+            self._promote_if_reached(self.lock_steps + t)
+            st = net.active_tiles
+            nv.ntuple_scores(self.boards, net.weights, net.cells, net.frac_bits, self.scores, self.targets, st)
             if self.learner == "tc":
                 nv.ntuple_tc_accumulate(self.prev_after, self.flag, self.targets, net.weights, net.cells, net.frac_bits, self.alpha,
-                                        self.acc, self.abs_acc, self.cnt, self.td_error)
+                                        self.acc, self.abs_acc, self.cnt, self.td_error, st)
                 nv.ntuple_tc_apply(self.prev_after, self.flag, net.cells, net.weights, self.acc, self.abs_acc, self.cnt, self.coh_e,
-                                   self.coh_a)
+                                   self.coh_a, st)
             else:
                 nv.ntuple_td_accumulate(self.prev_after, self.flag, self.targets, net.weights, net.cells, net.frac_bits, self.alpha,
-                                        self.acc, self.cnt, self.td_error)
-                nv.ntuple_td_apply(self.prev_after, self.flag, net.cells, net.weights, self.acc, self.cnt)
+                                        self.acc, self.cnt, self.td_error, st)
+                nv.ntuple_td_apply(self.prev_after, self.flag, net.cells, net.weights, self.acc, self.cnt, st)
             nv.policy_step_autoreset(subs[2 * t], subs[2 * t + 1], self.scores, self.targets, True, False, 0, self.boards, self.masks,
                                      self.ep_len, tr["boards"], tr["meta"], tr["rewards"], tr["logp"], tr["values"], B, 0,
                                      self.rng_mode)
@@ -277,16 +376,22 @@ class NTupleTrainer:
 
     def state_dict(self) -> dict:
         """The learner's own state (host tensors): ``learner``, ``alpha``, ``lock_steps`` and, for ``"tc"``, ``coh_e`` / ``coh_a``, so
-        that a resumed run keeps its rates.  The weights are the network's (``NTupleNetwork.save``); the envs start afresh."""
+        that a resumed run keeps its rates.  The weights are the network's (``NTupleNetwork.save``); the envs start afresh.  On a
+        multi-stage network also ``stages`` and ``promotions``."""
         out = {"learner": self.learner, "alpha": self.alpha, "lock_steps": self.lock_steps}
+        if self.network.stage_tiles is not None:
+            out.update(stages=self.network.stages, promotions=list(self.promotions))
         if self.learner == "tc":
             out.update(coh_e=self.coh_e.cpu().clone(), coh_a=self.coh_a.cpu().clone())
         return out
 
     def load_state_dict(self, state: dict) -> None:
-        """``ValueError`` for another learner's state or tables of another shape or dtype; nothing is changed then."""
+        """``ValueError`` for another learner's state, another stage count's, or tables of another shape or dtype; nothing is
+        changed then."""
         if state.get("learner") != self.learner:
             raise ValueError(f"the state is of learner {state.get('learner')!r}, the trainer's is {self.learner!r}")
+        if state.get("stages", 1) != self.network.stages:
+            raise ValueError(f"the state is of a network of {state.get('stages', 1)} stages, the trainer's has {self.network.stages}")
         tables = {}
         if self.learner == "tc":
             for k in ("coh_e", "coh_a"):
@@ -298,6 +403,7 @@ class NTupleTrainer:
         if not (alpha > 0.0 and np.isfinite(alpha)):
             raise ValueError(f"alpha must be a finite positive number, got {state['alpha']!r}")
         self.alpha, self.lock_steps = alpha, int(state["lock_steps"])
+        self.promotions = [(int(a), int(b)) for a, b in state.get("promotions", [])]
         for k, t in tables.items():
             getattr(self, k).copy_(t)
 

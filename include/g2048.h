@@ -502,6 +502,45 @@ int g2048_ntuple_tc_apply(const uint8_t *prev_after, const uint8_t *flag, int64_
                           int32_t *weights, int64_t *acc, int64_t *abs_acc, int32_t *cnt, int32_t *coh_e, int32_t *coh_a,
                           void *stream);
 
+/* ---- multi-stage n-tuple network (one set of tables per max-tile stage of the game) ----
+ * stage_tiles u8[n_stages - 1], a HOST pointer whose bytes travel in the kernarg: log2 tile values k_1 < k_2 < ... in 1 .. 17.
+ * n_stages S is 1 .. 8.  Every table of the network above (weights, acc, cnt, abs_acc, coh_e, coh_a) becomes [S][m][16^L], and
+ *   stage(x)     = #{ i : max over the 16 cells of x[c] >= k_i }   (the UNCLAMPED log2 tile: 16 and 17 count as themselves)
+ *   off(x, g, t) = ((stage(x) * m + t) << 4 L) + idx(view_g(x), t)  (idx as above, with its clamp)
+ * takes the place of t 16^L + idx in S(x); V, scores, the expectimax recursion, e, delta, acc / cnt / abs_acc / coh_e / coh_a and
+ * rdiv are exactly those above.  The stage is that of the board that is looked up: in scores the AFTERSTATE (a merge that
+ * creates tile k_i is valued by stage i's tables), in expectimax each leaf's afterstate, in the learners prev_after.  The
+ * maximum is the same in all eight views, so it is taken once per board.  S <= 8, m <= 8 and L <= 6 keep an offset below 2^30.
+ * The kernels know nothing of promotion: a caller whose upper stages are not split off yet passes the first p - 1 thresholds
+ * and n_stages = p, and boards at or above k_p are then served and learned by stage p - 1's tables.
+ * Each function has the unstaged signature with (stage_tiles, n_stages) after L, and the unstaged function IS the staged one
+ * called with (NULL, 1): one kernel per operation.  n_stages == 1 accepts a null stage_tiles (it is not read).
+ * G2048_EINVAL, before any device work, on top of every check of the unstaged function: n_stages outside 1 .. 8, a null
+ * stage_tiles with n_stages > 1, a threshold outside 1 .. 17, thresholds not strictly ascending.  g2048_ntuple_link and
+ * g2048_ntuple_expectimax_workspace_floats do not depend on the stages. */
+int g2048_ntuple_staged_values(const uint8_t *boards, int64_t n, const int32_t *weights, const uint8_t *tuple_cells /*host*/, int m,
+                               int L, const uint8_t *stage_tiles /*host*/, int n_stages, int frac_bits, float *values, void *stream);
+int g2048_ntuple_staged_scores(const uint8_t *boards, int64_t B, const int32_t *weights, const uint8_t *tuple_cells /*host*/, int m,
+                               int L, const uint8_t *stage_tiles /*host*/, int n_stages, int frac_bits, float *scores, float *values,
+                               void *stream);
+int g2048_ntuple_staged_expectimax(const uint8_t *boards, int64_t B, const int32_t *weights, const uint8_t *tuple_cells /*host*/,
+                                   int m, int L, const uint8_t *stage_tiles /*host*/, int n_stages, int frac_bits, int plies,
+                                   double gamma, float *workspace, float *scores, float *values, void *stream);
+int g2048_ntuple_staged_td_accumulate(const uint8_t *prev_after, const uint8_t *flag, const float *target, int64_t B,
+                                      const int32_t *weights, const uint8_t *tuple_cells /*host*/, int m, int L,
+                                      const uint8_t *stage_tiles /*host*/, int n_stages, int frac_bits, double alpha, int64_t *acc,
+                                      int32_t *cnt, float *td_error, void *stream);
+int g2048_ntuple_staged_td_apply(const uint8_t *prev_after, const uint8_t *flag, int64_t B, const uint8_t *tuple_cells /*host*/, int m,
+                                 int L, const uint8_t *stage_tiles /*host*/, int n_stages, int32_t *weights, int64_t *acc,
+                                 int32_t *cnt, void *stream);
+int g2048_ntuple_staged_tc_accumulate(const uint8_t *prev_after, const uint8_t *flag, const float *target, int64_t B,
+                                      const int32_t *weights, const uint8_t *tuple_cells /*host*/, int m, int L,
+                                      const uint8_t *stage_tiles /*host*/, int n_stages, int frac_bits, double alpha, int64_t *acc,
+                                      int64_t *abs_acc, int32_t *cnt, float *td_error, void *stream);
+int g2048_ntuple_staged_tc_apply(const uint8_t *prev_after, const uint8_t *flag, int64_t B, const uint8_t *tuple_cells /*host*/, int m,
+                                 int L, const uint8_t *stage_tiles /*host*/, int n_stages, int32_t *weights, int64_t *acc,
+                                 int64_t *abs_acc, int32_t *cnt, int32_t *coh_e, int32_t *coh_a, void *stream);
+
 /* ---- policy network (update): attention for 17-token sequences ------------------------------------- */
 
 /* softmax(q k^T * scale) v with attention dropout, head_dim 32, Sk = 17 keys, Sq = 17 queries (or 1: the CLS row

@@ -18,6 +18,9 @@ tools/probe_mc.py).
 ``--tc`` adds the TC learner (``NTupleTrainer(learner="tc")``, alpha 1.0) under the key "tc": its two launches tc_accumulate and
 tc_apply timed as td_accumulate and td_apply are in (a), in the same two board states of a TC trainer, and its training lock-step as
 in (b).  Without it the output is unchanged.
+``--stage-tiles 11 12 13 14`` adds (a) and (b) on a multi-stage network with those thresholds, every stage active, under the key
+"staged", in the same process: the cost of the stage (the max tile of every board looked up, S times the tables).
+``--only-kernels`` leaves (c) and (d) out.
 Prints one JSON line.
 """
 import argparse
@@ -58,7 +61,7 @@ def timed(fn, repeats, warmup=3, setup=None):
 def kernel_state(trainer, label, repeats):
     """The five kernels on the trainer's current boards / prev_after / flag."""
     net, B = trainer.network, trainer.num_envs
-    w, cells, F = net.weights, net.cells, net.frac_bits
+    w, cells, F, st = net.weights, net.cells, net.frac_bits, net.active_tiles
     m = net.m
     saved = w.clone()
     values = torch.empty(B, dtype=torch.float32, device=w.device)
@@ -70,12 +73,12 @@ def kernel_state(trainer, label, repeats):
 
     def accumulate():
         nv.ntuple_td_accumulate(trainer.prev_after, trainer.flag, trainer.targets, w, cells, F, trainer.alpha, trainer.acc, trainer.cnt,
-                                trainer.td_error)
+                                trainer.td_error, st)
 
     def prepare_apply():
         zero(), accumulate()
 
-    nv.ntuple_scores(trainer.boards, w, cells, F, trainer.scores, trainer.targets)
+    nv.ntuple_scores(trainer.boards, w, cells, F, trainer.scores, trainer.targets, st)
     zero(), accumulate()
     live = int((trainer.flag != 0).sum().item())
     res = {"state": label, "boards": B, "envs_with_predecessor": live,
@@ -84,10 +87,10 @@ def kernel_state(trainer, label, repeats):
                           "td_accumulate": f"{8 * m * live} gathers, {8 * m * live} 64-bit + {8 * m * live} 32-bit atomic adds",
                           "td_apply": f"{8 * m * live} atomic exchanges, one read-modify-write of weights and acc per distinct entry",
                           "link": f"{B} boards, 17 B in, 17 B out"}}
-    res["values"] = timed(lambda: nv.ntuple_values(trainer.boards, w, cells, F, values), repeats)
-    res["scores"] = timed(lambda: nv.ntuple_scores(trainer.boards, w, cells, F, trainer.scores, trainer.targets), repeats)
+    res["values"] = timed(lambda: nv.ntuple_values(trainer.boards, w, cells, F, values, st), repeats)
+    res["scores"] = timed(lambda: nv.ntuple_scores(trainer.boards, w, cells, F, trainer.scores, trainer.targets, st), repeats)
     res["td_accumulate"] = timed(accumulate, repeats, setup=zero)
-    res["td_apply"] = timed(lambda: nv.ntuple_td_apply(trainer.prev_after, trainer.flag, cells, w, trainer.acc, trainer.cnt), repeats,
+    res["td_apply"] = timed(lambda: nv.ntuple_td_apply(trainer.prev_after, trainer.flag, cells, w, trainer.acc, trainer.cnt, st), repeats,
                             setup=prepare_apply)
     res["link"] = timed(lambda: nv.ntuple_link(tr["boards"][0], tr["meta"][0], prev, flag), repeats)
     w.copy_(saved)  # the timed applies moved the weights
@@ -148,8 +151,15 @@ def tc_probe(boards, envs, dev, repeats, train_steps, chunk=50):
     return out
 
 
-def kernel_probe(B, dev, repeats, train_steps):
-    net = NTupleNetwork(device=dev)
+def staged_network(dev, stage_tiles):
+    """The default network, unstaged or with ``stage_tiles`` and every stage active from the start (promotion is not what is timed)."""
+    net = NTupleNetwork(device=dev, stage_tiles=stage_tiles)
+    net.active_stages = net.stages
+    return net
+
+
+def kernel_probe(B, dev, repeats, train_steps, stage_tiles=None):
+    net = staged_network(dev, stage_tiles)
     trainer = NTupleTrainer(net, B, device=dev)
     trainer.train(1)
     out = [kernel_state(trainer, "reset: one lock-step after a reset of all boards", repeats)]
@@ -158,8 +168,8 @@ def kernel_probe(B, dev, repeats, train_steps):
     return out
 
 
-def train_probe(B, dev, repeats, chunk=50):
-    trainer = NTupleTrainer(NTupleNetwork(device=dev), B, device=dev)
+def train_probe(B, dev, repeats, chunk=50, stage_tiles=None):
+    trainer = NTupleTrainer(staged_network(dev, stage_tiles), B, device=dev)
     t = timed(lambda: trainer.train(chunk), repeats)
     return {"envs": B, "lock_steps_per_call": chunk, **{k.replace("_ms", "_ms_per_lock_step"): round(v / chunk, 4) for k, v in t.items()}}
 
@@ -199,6 +209,9 @@ def main():
     ap.add_argument("--board-steps", type=int, default=48)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--tc", action="store_true", help="also time the TC learner's two launches and its training lock-step")
+    ap.add_argument("--stage-tiles", type=int, nargs="+", default=None, metavar="K",
+                    help="also time the kernels and the training lock-step on a multi-stage network with these thresholds")
+    ap.add_argument("--only-kernels", action="store_true", help="(a) and (b) only: no player lock-step, no learning speed")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -217,12 +230,21 @@ def main():
     for B in a.envs:
         res["training_lock_step"].append(train_probe(B, dev, a.repeats))
         print(json.dumps(res["training_lock_step"][-1]), flush=True)
+    if a.stage_tiles:
+        res["staged"] = {"stage_tiles": a.stage_tiles, "stages": len(a.stage_tiles) + 1, "active_stages": len(a.stage_tiles) + 1,
+                         "kernels": [], "training_lock_step": []}
+        for B in a.boards:
+            res["staged"]["kernels"] += kernel_probe(B, dev, a.repeats, a.train_steps, a.stage_tiles)
+            print(json.dumps(res["staged"]["kernels"][-2:]), flush=True)
+        for B in a.envs:
+            res["staged"]["training_lock_step"].append(train_probe(B, dev, a.repeats, stage_tiles=a.stage_tiles))
+            print(json.dumps(res["staged"]["training_lock_step"][-1]), flush=True)
     net = NTupleNetwork(device=dev)
-    for B in a.player_boards:
+    for B in ([] if a.only_kernels else a.player_boards):
         res["player_lock_step"].append(lockstep_probe(net, agent, B, dev, a.repeats, a.board_steps))
         print(json.dumps(res["player_lock_step"][-1]), flush=True)
     del net
-    for B in a.envs:
+    for B in ([] if a.only_kernels else a.envs):
         res["learning"].append(learning_probe(B, dev, a.learn_steps, a.episodes))
         print(json.dumps(res["learning"][-1]), flush=True)
     if a.tc:
