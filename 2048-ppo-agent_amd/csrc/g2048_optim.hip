@@ -52,6 +52,7 @@ struct StepArgs {
 // per-group constants of one step, derived once (by workgroup 0 of k_opt_sqnorm) from the f64 hyper-parameters and the step
 // count: the two f64 pow calls of the bias corrections cost microseconds and must not sit in every workgroup of the update
 struct Derived { float step_size, inv_bc2_sqrt, lr_wd, w1, b2, w2, eps, inv_scale; };  // inv_scale: of the scaler BEFORE this step's update
+static_assert(sizeof(Derived) == 32, "workspace layout");
 
 __global__ void __launch_bounds__(OPT_THREADS)
 k_opt_sqnorm(const g2048_opt_chunk *__restrict__ chunks, const float *__restrict__ grads, float *__restrict__ partial, StepArgs A,
