@@ -16,6 +16,10 @@ and records the coherence numbers (entries with a rate, their mean rate) at ever
 splits a stage off at the first check, every ``--promote-every`` lock-steps, at which a training board has reached its threshold.
 The result records ``stage_tiles``, every promotion (lock-step, training seconds at the end of its chunk) and ``active_stages`` at
 every evaluation point.
+``--carousel`` turns carousel shaping on with the network's stage thresholds (``NTupleTrainer(carousel_tiles="stages")``: episodes
+start in turn at every stage, from pools of boards at which games entered it), ``--carousel-tiles K ...`` with thresholds of its own
+(on any network).  The result records ``carousel_tiles`` and, at every evaluation point, ``carousel_starts``: the episode starts per
+stage so far (index 0: fresh boards, fallbacks included).
 """
 import argparse
 import json
@@ -46,22 +50,28 @@ def main():
     ap.add_argument("--stage-tiles", type=int, nargs="+", default=None, metavar="K",
                     help="log2 tile thresholds of a multi-stage network, ascending (11 12 13 14: a stage from 2048, 4096, 8192, 16384)")
     ap.add_argument("--promote-every", type=int, default=64, metavar="N", help="lock-steps between two promotion checks (0: never)")
+    ap.add_argument("--carousel", action="store_true", help="carousel shaping over the network's --stage-tiles")
+    ap.add_argument("--carousel-tiles", type=int, nargs="+", default=None, metavar="K",
+                    help="carousel shaping over these log2 tile thresholds, ascending (instead of --carousel)")
     ap.add_argument("--chunk", type=int, default=50, help="lock-steps between two looks at the clock")
     ap.add_argument("--seed", type=int, default=0, help="seed of the training environments")
     ap.add_argument("--out", default=None, help="write the JSON result here")
     ap.add_argument("--save", default=None, help="save the trained network here")
     args = ap.parse_args()
+    if args.carousel and args.carousel_tiles:
+        ap.error("--carousel takes the network's thresholds, --carousel-tiles its own: give one of them")
 
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     net = NTupleNetwork(device=dev, stage_tiles=args.stage_tiles)
     trainer = NTupleTrainer(net, args.envs, alpha=args.alpha, seed=args.seed, device=dev, learner=args.learner,
-                            promote_every=args.promote_every)
+                            promote_every=args.promote_every, carousel_tiles="stages" if args.carousel else args.carousel_tiles)
     budget = args.minutes * 60.0
     points = sorted(60.0 * m for m in args.eval_at) if args.eval_at else [budget * (k + 1) / args.evals for k in range(max(args.evals, 1))]
     result = dict(envs=args.envs, learner=args.learner, alpha=args.alpha, seed=args.seed, tuples=[list(t) for t in net.tuples],
                   frac_bits=net.frac_bits, minutes=args.minutes, first_2048=None, evaluations=[],
-                  stage_tiles=None if net.stage_tiles is None else list(net.stage_tiles), promote_every=args.promote_every, promotions=[])
+                  stage_tiles=None if net.stage_tiles is None else list(net.stage_tiles), promote_every=args.promote_every, promotions=[],
+                  carousel_tiles=None if trainer.carousel_tiles is None else list(trainer.carousel_tiles))
     trained = 0.0
     episodes = 0
     while points:
@@ -89,6 +99,8 @@ def main():
                           max_abs_weight=int(net.weights.abs().max().item()), active_stages=net.active_stages)
                 if coherence is not None:
                     ev.update(coherence=coherence)
+                if trainer.starts is not None:
+                    ev.update(carousel_starts=trainer.starts.cpu().tolist())
                 result["evaluations"].append(ev)
                 print(f"{trained / 60:.2f} min, {trainer.lock_steps} lock-steps, plies {plies}: mean max tile "
                       f"{ev['mean_max_tile']:.1f}, percent {ev['percent']}", flush=True)

@@ -627,6 +627,41 @@ def ntuple_link(tr_boards_row, tr_meta_row, prev_after, flag):
            "g2048_ntuple_link")
 
 
+def _exact(t, dtype, shape, name: str, optional=False):
+    """``_dev`` plus the exact shape."""
+    if t is not None and tuple(t.shape) != tuple(shape):
+        raise NativeError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    return _dev(t, dtype, None, name, optional)
+
+
+def ntuple_carousel_record(boards, masks, flag, carousel_tiles, reached, pool_boards, pool_masks):
+    """The record half of the carousel: every env with flag == 1 whose board u8 [B,16] has entered carousel stage s > reached u8 [B]
+    puts board and mask into slot (s - 1, b) of pool_boards u8 [n,B,16] / pool_masks u8 [n,B], reached = s.  ``carousel_tiles``:
+    the n ascending log2 tile thresholds (host)."""
+    st, S = _stages(carousel_tiles)
+    n, B = S - 1, flag.numel()
+    _check(load().g2048_ntuple_carousel_record(_exact(boards, u8, (B, 16), "boards"), _exact(masks, u8, (B,), "masks"),
+                                               _exact(flag, u8, (B,), "flag"), B, st.ctypes.data, n,
+                                               _exact(reached, u8, (B,), "reached"), _exact(pool_boards, u8, (n, B, 16), "pool_boards"),
+                                               _exact(pool_masks, u8, (n, B), "pool_masks"), _stream()),
+           "g2048_ntuple_carousel_record")
+
+
+def ntuple_carousel_restart(sub, flag, pool_boards, pool_masks, boards, masks, reached, turn, starts, rng_mode: int, start_stage=None):
+    """The restart half: every env with flag == 2 takes its turn (turn i32 [B], the bits of a u32) and starts its episode at a donor's
+    pool board of the turn's stage if there is one, else at the fresh board it holds; starts i64 [n + 1] counts per stage.  ``sub``:
+    the lock-step's act sub-key (host u32 [2]).  start_stage u8 [B] or None: the stage per restarted env, 0xFF elsewhere."""
+    B = flag.numel()
+    n = pool_masks.shape[0] if pool_masks is not None and pool_masks.dim() == 2 else 0
+    _check(load().g2048_ntuple_carousel_restart(int(sub[0]), int(sub[1]), _exact(flag, u8, (B,), "flag"), B, n,
+                                                _exact(pool_boards, u8, (n, B, 16), "pool_boards"),
+                                                _exact(pool_masks, u8, (n, B), "pool_masks"), _exact(boards, u8, (B, 16), "boards"),
+                                                _exact(masks, u8, (B,), "masks"), _exact(reached, u8, (B,), "reached"),
+                                                _exact(turn, KEY_DTYPE, (B,), "turn"), _exact(starts, i64, (n + 1,), "starts"),
+                                                _exact(start_stage, u8, (B,), "start_stage", optional=True), int(rng_mode), _stream()),
+           "g2048_ntuple_carousel_restart")
+
+
 def attn_fwd(q_ptr: int, k_ptr: int, v_ptr: int, o, lse, B: int, H: int, Sq: int, strides, scale: float, p_drop: float,
              seed: int, seed_state: int = 0):
     """q/k/v: raw device addresses inside bf16 tensors the caller keeps alive; strides = (q_sb, q_ss, k_sb, k_ss,

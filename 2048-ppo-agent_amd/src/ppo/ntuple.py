@@ -79,6 +79,23 @@ def _check_stage_tiles(stage_tiles):
     return tiles
 
 
+def _check_carousel_tiles(carousel_tiles, network):
+    """-> None (no carousel) or the carousel's thresholds as a tuple of ints: ``"stages"`` is the network's ``stage_tiles``,
+    anything else goes through the rules of ``stage_tiles``."""
+    if carousel_tiles is None:
+        return None
+    if isinstance(carousel_tiles, str):
+        if carousel_tiles != "stages":
+            raise ValueError(f"carousel_tiles must be None, 'stages' or a sequence of log2 tile values, got {carousel_tiles!r}")
+        if network.stage_tiles is None:
+            raise ValueError("carousel_tiles='stages' needs a multi-stage network; give an unstaged one thresholds of its own")
+        return network.stage_tiles
+    try:
+        return _check_stage_tiles(carousel_tiles)
+    except ValueError as e:
+        raise ValueError(str(e).replace("stage_tiles", "carousel_tiles")) from None
+
+
 def _device(device) -> torch.device:
     return C.device() if device is None else torch.device(device)
 
@@ -264,12 +281,28 @@ class NTupleTrainer:
     the next threshold, several times at one check if need be.  ``promote_every=0`` never promotes.  A new stage's ``coh_e`` /
     ``coh_a`` stay zero (rate 1).  ``promotions`` lists ``(lock_steps, new active_stages)``.  The count is global, so
     ``train(48)`` and ``train(20); train(28)`` give the same bits.
+
+    ``carousel_tiles`` turns carousel shaping on (Jaskowski 2017): episodes no longer all start from an empty board but go round
+    the stages of the game, so tables for late boards get as many episode starts as those for early ones.  ``None`` (the default)
+    is off: nothing is allocated and the launches are the five above.  ``"stages"`` takes the network's ``stage_tiles`` (a
+    ``ValueError`` on an unstaged network); a sequence gives the carousel thresholds of its own, under the rules of
+    ``stage_tiles``, on any network.  All of them are always in use, whatever ``active_stages`` is.  With n thresholds a lock-step
+    gets two more launches after ``link``: ``carousel_record`` puts the board of an env whose episode has entered carousel stage
+    s (the number of thresholds at or below its largest tile) into the env's slot of ``pool_boards`` u8 [n, B, 16] /
+    ``pool_masks`` u8 [n, B] (a slot is empty while its mask is 0; ``reached`` u8 [B] is the highest stage recorded in the
+    running episode), and ``carousel_restart`` sends an env whose episode has just ended to stage c = (b + ``turn[b]``) mod
+    (n + 1) (``turn`` i32 [B], the bits of a u32 count of the env's restarts): c = 0 keeps the engine's fresh board, c >= 1 takes
+    the board in slot (c - 1, j) of a donor env j drawn from the lock-step's act sub-key (which the greedy step does not use),
+    and falls back to the fresh board if that slot is empty.  ``starts`` i64 [n + 1] counts the episode starts per stage, the
+    fallbacks under 0.  The learner is untouched: an ended episode's last update has target 0, and the first ``link`` after a
+    restart takes the afterstate of the move played on the pool board.  The key chain advances as without the carousel.  The
+    pools, ``reached``, ``turn`` and ``starts`` are env state: they are not in ``state_dict()`` and start afresh on resume.
     """
 
     LEARNERS = ("td0", "tc")
 
     def __init__(self, network: NTupleNetwork, num_envs: int, alpha: float = 0.1, seed: int = 0, rng_mode=None, device=None,
-                 learner: str = "td0", promote_every: int = 64):
+                 learner: str = "td0", promote_every: int = 64, carousel_tiles=None):
         if learner not in self.LEARNERS:
             raise ValueError(f"learner must be one of {self.LEARNERS}, got {learner!r}")
         if isinstance(promote_every, bool) or not isinstance(promote_every, (int, np.integer)) or promote_every < 0:
@@ -280,6 +313,7 @@ class NTupleTrainer:
             raise ValueError(f"num_envs must be positive, got {num_envs!r}")
         if not (float(alpha) > 0.0 and np.isfinite(float(alpha))):
             raise ValueError(f"alpha must be a finite positive number, got {alpha!r}")
+        self.carousel_tiles = _check_carousel_tiles(carousel_tiles, network)
         self.network = network
         self.num_envs = B = int(num_envs)
         self.alpha = float(alpha)
@@ -313,6 +347,15 @@ class NTupleTrainer:
         self.lock_steps = 0
         self.promote_every = int(promote_every)
         self.promotions = []
+        self.pool_boards = self.pool_masks = self.reached = self.turn = self.starts = None
+        if self.carousel_tiles is not None:
+            n = len(self.carousel_tiles)
+            self._carousel = np.array(self.carousel_tiles, np.uint8)
+            self.pool_boards = torch.zeros((n, B, 16), dtype=u8, device=dev)
+            self.pool_masks = torch.zeros((n, B), dtype=u8, device=dev)
+            self.reached = torch.zeros(B, dtype=u8, device=dev)
+            self.turn = torch.zeros(B, dtype=nv.KEY_DTYPE, device=dev)  # u32 counts, carried as i32 like the keys
+            self.starts = torch.zeros(n + 1, dtype=torch.int64, device=dev)
 
     def _promote_if_reached(self, count: int) -> None:
         """The promotion check in front of lock-step ``count`` (see the class docstring)."""
@@ -327,7 +370,8 @@ class NTupleTrainer:
     def train(self, lock_steps: int, record: bool = False):
         """``lock_steps`` lock-steps -> {"episodes": i64 [], "td_sq_sum": f64 []} (device tensors: episodes finished, sum of
         td_error^2).  ``record=True`` adds per-step copies "boards" u8 [T, B, 16] (before the step), "meta" u8 [T, B], "scores"
-        f32 [T, B, 4] and "targets" f32 [T, B]: for replaying a run in a test, not for training."""
+        f32 [T, B, 4] and "targets" f32 [T, B]: for replaying a run in a test, not for training.  With the carousel on it also adds
+        "start_stage" u8 [T, B]: the stage at which an env restarted after the step (0: a fresh board), 0xFF where it did not."""
         T, B, net, tr = int(lock_steps), self.num_envs, self.network, self._tr
         if T < 1:
             raise ValueError(f"lock_steps must be positive, got {lock_steps!r}")
@@ -344,6 +388,8 @@ class NTupleTrainer:
                        meta=torch.empty((T, B), dtype=torch.uint8, device=self.device),
                        scores=torch.empty((T, B, 4), dtype=torch.float32, device=self.device),
                        targets=torch.empty((T, B), dtype=torch.float32, device=self.device))
+            if self.carousel_tiles is not None:
+                rec["start_stage"] = torch.empty((T, B), dtype=torch.uint8, device=self.device)
         for t in range(T):
             self._promote_if_reached(self.lock_steps + t)
             st = net.active_tiles
@@ -361,6 +407,12 @@ class NTupleTrainer:
                                      self.ep_len, tr["boards"], tr["meta"], tr["rewards"], tr["logp"], tr["values"], B, 0,
                                      self.rng_mode)
             nv.ntuple_link(tr["boards"][0], tr["meta"][0], self.prev_after, self.flag)
+            if self.carousel_tiles is not None:
+                nv.ntuple_carousel_record(self.boards, self.masks, self.flag, self._carousel, self.reached, self.pool_boards,
+                                          self.pool_masks)
+                nv.ntuple_carousel_restart(subs[2 * t], self.flag, self.pool_boards, self.pool_masks, self.boards, self.masks,
+                                           self.reached, self.turn, self.starts, self.rng_mode,
+                                           None if rec is None else rec["start_stage"][t])
             episodes += (self.flag == 2).sum()
             td_sq += self.td_error.double().square().sum()
             if rec is not None:
@@ -377,19 +429,25 @@ class NTupleTrainer:
     def state_dict(self) -> dict:
         """The learner's own state (host tensors): ``learner``, ``alpha``, ``lock_steps`` and, for ``"tc"``, ``coh_e`` / ``coh_a``, so
         that a resumed run keeps its rates.  The weights are the network's (``NTupleNetwork.save``); the envs start afresh.  On a
-        multi-stage network also ``stages`` and ``promotions``."""
+        multi-stage network also ``stages`` and ``promotions``; with the carousel on also ``carousel_tiles`` (the thresholds only:
+        the pools are env state and start afresh on resume)."""
         out = {"learner": self.learner, "alpha": self.alpha, "lock_steps": self.lock_steps}
         if self.network.stage_tiles is not None:
             out.update(stages=self.network.stages, promotions=list(self.promotions))
+        if self.carousel_tiles is not None:
+            out.update(carousel_tiles=tuple(self.carousel_tiles))
         if self.learner == "tc":
             out.update(coh_e=self.coh_e.cpu().clone(), coh_a=self.coh_a.cpu().clone())
         return out
 
     def load_state_dict(self, state: dict) -> None:
-        """``ValueError`` for another learner's state, another stage count's, or tables of another shape or dtype; nothing is
-        changed then."""
+        """``ValueError`` for another learner's state, another stage count's, other carousel thresholds (none counts as other), or
+        tables of another shape or dtype; nothing is changed then."""
         if state.get("learner") != self.learner:
             raise ValueError(f"the state is of learner {state.get('learner')!r}, the trainer's is {self.learner!r}")
+        theirs = state.get("carousel_tiles")
+        if (None if theirs is None else tuple(int(k) for k in theirs)) != self.carousel_tiles:
+            raise ValueError(f"the state is of carousel thresholds {theirs!r}, the trainer's are {self.carousel_tiles!r}")
         if state.get("stages", 1) != self.network.stages:
             raise ValueError(f"the state is of a network of {state.get('stages', 1)} stages, the trainer's has {self.network.stages}")
         tables = {}

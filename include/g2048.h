@@ -541,6 +541,40 @@ int g2048_ntuple_staged_tc_apply(const uint8_t *prev_after, const uint8_t *flag,
                                  int L, const uint8_t *stage_tiles /*host*/, int n_stages, int32_t *weights, int64_t *acc,
                                  int64_t *abs_acc, int32_t *cnt, int32_t *coh_e, int32_t *coh_a, void *stream);
 
+/* ---- n-tuple carousel (carousel shaping: episode starts from per-stage pools of boards, so every stage is trained) ----
+ * For a trainer over B always-live envs, after the auto-reset env step and g2048_ntuple_link of a lock-step.  The carousel has its
+ * own thresholds carousel_tiles u8[n_tiles], a HOST pointer whose bytes travel in the kernarg: log2 tile values k_1 < ... < k_n in
+ * 1 .. 17, n in 1 .. 7, all always in use, and
+ *   cs(x) = #{ i : max over the 16 cells of x[c] >= k_i }            (the UNCLAMPED log2 tile: stage(x) above over these thresholds)
+ * State, all-zero at the start: pool_boards u8[n][B][16] and pool_masks u8[n][B] (slot (i, b) belongs to env b and is empty exactly
+ * when its mask is 0), reached u8[B] (the highest carousel stage env b's episode has recorded), turn u32[B], starts i64[n + 1].
+ * flag is g2048_ntuple_link's: 1 the episode goes on, 2 the step ended it and boards / masks hold the engine's fresh board.
+ *   record:  for every env b with flag == 1 and s = cs(boards[b]) > reached[b]: pool_boards[s-1][b] = boards[b],
+ *            pool_masks[s-1][b] = masks[b] (as it is, also 0), reached[b] = s.  Only slot s - 1, also when s jumps by several.
+ *   restart: for every env b with flag == 2: turn[b] += 1 (u32 wrap), c = (u32)(b + turn[b]) % (n + 1).  If c >= 1:
+ *            j = bits(split(sub, B)[b]) % B (32 bits, shape ()), and if pool_masks[c-1][j] != 0: boards[b] = pool_boards[c-1][j],
+ *            masks[b] = pool_masks[c-1][j], reached[b] = c, starts[c] += 1, start_stage[b] = c.  In every other case the fresh
+ *            board stays, reached[b] = 0, starts[0] += 1, start_stage[b] = 0.  An env with flag != 2: start_stage[b] = 0xFF only.
+ * record writes only the env's own slots and restart writes no slot: neither launch races with itself.  restart reads what the
+ * same lock-step's record wrote, so they are two launches.  All of it is integer arithmetic; starts is updated by 64-bit atomic
+ * adds, so nothing depends on scheduling. */
+
+/* The record half.  boards u8[B][16] / masks u8[B]: the envs' state for the next step.  One lane per env.
+ * G2048_EINVAL, before any device work: a null pointer, B outside 1 .. 2^28, n_tiles outside 1 .. 7, a threshold outside 1 .. 17,
+ * thresholds not strictly ascending, boards or pool_boards not 16-byte aligned. */
+int g2048_ntuple_carousel_record(const uint8_t *boards, const uint8_t *masks, const uint8_t *flag, int64_t B,
+                                 const uint8_t *carousel_tiles /*host*/, int n_tiles, uint8_t *reached,
+                                 uint8_t *pool_boards, uint8_t *pool_masks, void *stream);
+
+/* The restart half, in a launch of its own after g2048_ntuple_carousel_record.  (sub0, sub1): the lock-step's act sub-key, from
+ * which a greedy step (sample == 0) draws nothing.  start_stage u8[B] may be NULL.  One lane per env.
+ * G2048_EINVAL, before any device work: a null pointer other than start_stage, B outside 1 .. 2^28, n_tiles outside 1 .. 7, an
+ * unknown rng_mode, boards or pool_boards not 16-byte aligned, turn not 4-byte aligned, starts not 8-byte aligned. */
+int g2048_ntuple_carousel_restart(uint32_t sub0, uint32_t sub1, const uint8_t *flag, int64_t B, int n_tiles,
+                                  const uint8_t *pool_boards, const uint8_t *pool_masks, uint8_t *boards, uint8_t *masks,
+                                  uint8_t *reached, uint32_t *turn, int64_t *starts, uint8_t *start_stage /*may be NULL*/,
+                                  int rng_mode, void *stream);
+
 /* ---- policy network (update): attention for 17-token sequences ------------------------------------- */
 
 /* softmax(q k^T * scale) v with attention dropout, head_dim 32, Sk = 17 keys, Sq = 17 queries (or 1: the CLS row

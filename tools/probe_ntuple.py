@@ -21,6 +21,11 @@ in (b).  Without it the output is unchanged.
 ``--stage-tiles 11 12 13 14`` adds (a) and (b) on a multi-stage network with those thresholds, every stage active, under the key
 "staged", in the same process: the cost of the stage (the max tile of every board looked up, S times the tables).
 ``--only-kernels`` leaves (c) and (d) out.
+``--carousel`` measures carousel shaping instead of all of the above and writes ``profiles/ntuple_carousel_probe.json`` unless
+``--out`` says otherwise: at every ``--boards`` env count two TD(0) trainers of the default network, one with
+``carousel_tiles=--carousel-tiles`` and one without, each ``--train-steps`` lock-steps into training; the two launches
+carousel_record and carousel_restart on the first one's state, and the whole training lock-step of both, alternating on, off, on,
+off in the same process.
 Prints one JSON line.
 """
 import argparse
@@ -151,6 +156,38 @@ def tc_probe(boards, envs, dev, repeats, train_steps, chunk=50):
     return out
 
 
+def carousel_probe(boards, dev, repeats, train_steps, tiles, chunk=50):
+    out = {"carousel_tiles": list(tiles), "learner": "td0, alpha 0.1", "train_steps": train_steps, "kernels": [], "training_lock_step": []}
+    for B in boards:
+        on = NTupleTrainer(NTupleNetwork(device=dev), B, device=dev, carousel_tiles=tiles)
+        off = NTupleTrainer(NTupleNetwork(device=dev), B, device=dev)
+        on.train(train_steps), off.train(train_steps)
+        saved = [t.clone() for t in (on.boards, on.masks, on.reached, on.turn, on.starts)]
+        sub = (0x12345678, 0x9ABCDEF0)
+        flag2 = int((on.flag == 2).sum().item())
+        res = {"boards": B, "envs_restarting": flag2, "pool_slots_filled": on.pool_masks.ne(0).sum(dim=1).cpu().tolist(),
+               "starts_so_far": on.starts.cpu().tolist(),
+               "per_launch": {"carousel_record": f"{B} flags, 17 B in per env whose episode goes on, 17 B out per env that records",
+                              "carousel_restart": f"{B} flags; per restarting env ({flag2}) two threefry blocks, <= 17 B in, <= 22 B out, "
+                                                  "one 64-bit atomic add"}}
+        res["carousel_record"] = timed(lambda: nv.ntuple_carousel_record(on.boards, on.masks, on.flag, on.carousel_tiles, on.reached,
+                                                                         on.pool_boards, on.pool_masks), repeats)
+        res["carousel_restart"] = timed(lambda: nv.ntuple_carousel_restart(sub, on.flag, on.pool_boards, on.pool_masks, on.boards, on.masks,
+                                                                           on.reached, on.turn, on.starts, on.rng_mode), repeats)
+        for t, s in zip((on.boards, on.masks, on.reached, on.turn, on.starts), saved):  # the timed restarts moved them
+            t.copy_(s)
+        out["kernels"].append(res)
+        print(json.dumps(res), flush=True)
+        for run in (1, 2):
+            for name, trainer in (("on", on), ("off", off)):
+                t = timed(lambda: trainer.train(chunk), repeats)
+                out["training_lock_step"].append({"envs": B, "carousel": name, "run": run, "lock_steps_per_call": chunk,
+                                                  **{k.replace("_ms", "_ms_per_lock_step"): round(v / chunk, 4) for k, v in t.items()}})
+                print(json.dumps(out["training_lock_step"][-1]), flush=True)
+        del on, off
+    return out
+
+
 def staged_network(dev, stage_tiles):
     """The default network, unstaged or with ``stage_tiles`` and every stage active from the start (promotion is not what is timed)."""
     net = NTupleNetwork(device=dev, stage_tiles=stage_tiles)
@@ -211,6 +248,9 @@ def main():
     ap.add_argument("--tc", action="store_true", help="also time the TC learner's two launches and its training lock-step")
     ap.add_argument("--stage-tiles", type=int, nargs="+", default=None, metavar="K",
                     help="also time the kernels and the training lock-step on a multi-stage network with these thresholds")
+    ap.add_argument("--carousel", action="store_true", help="measure carousel shaping only (see above)")
+    ap.add_argument("--carousel-tiles", type=int, nargs="+", default=[7, 8, 9, 10], metavar="K",
+                    help="the carousel's thresholds for --carousel (low enough that the pools fill within --train-steps)")
     ap.add_argument("--only-kernels", action="store_true", help="(a) and (b) only: no player lock-step, no learning speed")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -218,6 +258,16 @@ def main():
         raise SystemExit("probe_ntuple.py measures on the GPU; none is visible")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
+    if a.carousel:
+        res = {"command": "python tools/probe_ntuple.py " + " ".join(sys.argv[1:]), "device": torch.cuda.get_device_name(dev),
+               "network": "4 x 6-tuples (default), frac_bits 12, alpha 0.1", "repeats": a.repeats,
+               "timer": "HIP events around one call, 3 warm-up calls, median [min, max]",
+               "carousel": carousel_probe(a.boards, dev, a.repeats, a.train_steps, a.carousel_tiles)}
+        print(json.dumps(res))
+        out = a.out or os.path.join(HERE, "..", "profiles", "ntuple_carousel_probe.json")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        json.dump(res, open(out, "w"), indent=1)
+        return
     torch.manual_seed(0)
     agent = PPOAgent(**MODEL).to(dev).eval()
     res = {"command": "python tools/probe_ntuple.py " + " ".join(sys.argv[1:]), "device": torch.cuda.get_device_name(dev),
