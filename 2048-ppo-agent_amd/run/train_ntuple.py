@@ -20,6 +20,9 @@ every evaluation point.
 start in turn at every stage, from pools of boards at which games entered it), ``--carousel-tiles K ...`` with thresholds of its own
 (on any network).  The result records ``carousel_tiles`` and, at every evaluation point, ``carousel_starts``: the episode starts per
 stage so far (index 0: fresh boards, fallbacks included).
+``--lam 0.5`` turns delayed TD(lambda) / TC(lambda) on for either learner (``NTupleTrainer(lam=...)``: an afterstate is updated once,
+``--horizon`` - 1 lock-steps late, by the lambda-sum of the errors since; the default horizon is the smallest h with lam^h <= 0.1,
+capped at 8).  The result records ``lam`` and ``horizon``.
 """
 import argparse
 import json
@@ -53,6 +56,8 @@ def main():
     ap.add_argument("--carousel", action="store_true", help="carousel shaping over the network's --stage-tiles")
     ap.add_argument("--carousel-tiles", type=int, nargs="+", default=None, metavar="K",
                     help="carousel shaping over these log2 tile thresholds, ascending (instead of --carousel)")
+    ap.add_argument("--lam", type=float, default=None, help="delayed TD(lambda) / TC(lambda) with this lambda in [0, 1] (default: off)")
+    ap.add_argument("--horizon", type=int, default=None, metavar="H", help="its horizon, 1 .. 8 (default: the smallest h with lam^h <= 0.1)")
     ap.add_argument("--chunk", type=int, default=50, help="lock-steps between two looks at the clock")
     ap.add_argument("--seed", type=int, default=0, help="seed of the training environments")
     ap.add_argument("--out", default=None, help="write the JSON result here")
@@ -65,13 +70,15 @@ def main():
     torch.cuda.set_device(dev)
     net = NTupleNetwork(device=dev, stage_tiles=args.stage_tiles)
     trainer = NTupleTrainer(net, args.envs, alpha=args.alpha, seed=args.seed, device=dev, learner=args.learner,
-                            promote_every=args.promote_every, carousel_tiles="stages" if args.carousel else args.carousel_tiles)
+                            promote_every=args.promote_every, carousel_tiles="stages" if args.carousel else args.carousel_tiles,
+                            lam=args.lam, horizon=args.horizon)
     budget = args.minutes * 60.0
     points = sorted(60.0 * m for m in args.eval_at) if args.eval_at else [budget * (k + 1) / args.evals for k in range(max(args.evals, 1))]
     result = dict(envs=args.envs, learner=args.learner, alpha=args.alpha, seed=args.seed, tuples=[list(t) for t in net.tuples],
                   frac_bits=net.frac_bits, minutes=args.minutes, first_2048=None, evaluations=[],
                   stage_tiles=None if net.stage_tiles is None else list(net.stage_tiles), promote_every=args.promote_every, promotions=[],
-                  carousel_tiles=None if trainer.carousel_tiles is None else list(trainer.carousel_tiles))
+                  carousel_tiles=None if trainer.carousel_tiles is None else list(trainer.carousel_tiles),
+                  lam=trainer.lam, horizon=trainer.horizon)
     trained = 0.0
     episodes = 0
     while points:

@@ -662,6 +662,59 @@ def ntuple_carousel_restart(sub, flag, pool_boards, pool_masks, boards, masks, r
            "g2048_ntuple_carousel_restart")
 
 
+def _ring(hist, hist_len, B: int):
+    """The delayed learner's ring: hist u8 [h, B, 16], hist_len u8 [B] -> (hist pointer, hist_len pointer, h)."""
+    h = hist.shape[0] if hist is not None and hist.dim() == 3 else 0
+    return _exact(hist, u8, (h, B, 16), "hist"), _exact(hist_len, u8, (B,), "hist_len"), h
+
+
+def ntuple_delayed_accumulate(hist, hist_err, hist_len, flag, target, head: int, lam: float, weights, tuple_cells, frac_bits: int,
+                              alpha: float, acc, abs_acc, cnt, td_error=None, stage_tiles=None):
+    """The accumulate half of one delayed TD(lambda) / TC(lambda) lock-step over the ring hist u8 [h, B, 16] / hist_err f32 [h, B] /
+    hist_len u8 [B] whose newest afterstate is in slot ``head``: e of that afterstate -> td_error and hist_err[head]; acc += delta_j,
+    cnt += 1 (abs_acc += |delta_j| unless ``abs_acc`` is None: TD) at the entries of every DUE state of every env with flag != 0,
+    delta_j from the lambda-sum of the errors since.  The tables are [m, 16^L], or [S, m, 16^L] with ``stage_tiles``."""
+    cells, m, L = _tuple_cells(tuple_cells)
+    B = flag.numel()
+    st, S = (None, 1) if stage_tiles is None else _stages(stage_tiles)
+    E = S * m * 16 ** L
+    p_hist, p_len, h = _ring(hist, hist_len, B)
+    _check(load().g2048_ntuple_delayed_accumulate(p_hist, _exact(hist_err, f32, (h, B), "hist_err"), p_len, _exact(flag, u8, (B,), "flag"),
+                                                  _dev(target, f32, B, "target"), B, h, int(head), float(lam),
+                                                  _dev(weights, i32, E, "weights"), cells.ctypes.data, m, L,
+                                                  None if st is None else st.ctypes.data, S, int(frac_bits), float(alpha),
+                                                  _dev(acc, i64, E, "acc"), _dev(abs_acc, i64, E, "abs_acc", optional=True),
+                                                  _dev(cnt, i32, E, "cnt"), _dev(td_error, f32, B, "td_error", optional=True), _stream()),
+           "g2048_ntuple_delayed_accumulate")
+
+
+def ntuple_delayed_apply(hist, hist_len, flag, head: int, tuple_cells, weights, acc, abs_acc, cnt, coh_e, coh_a, stage_tiles=None):
+    """The apply half over the same due states: td_apply per due board with ``abs_acc``, ``coh_e`` and ``coh_a`` all None, tc_apply with
+    none of them None."""
+    cells, m, L = _tuple_cells(tuple_cells)
+    B = flag.numel()
+    st, S = (None, 1) if stage_tiles is None else _stages(stage_tiles)
+    E = S * m * 16 ** L
+    p_hist, p_len, h = _ring(hist, hist_len, B)
+    _check(load().g2048_ntuple_delayed_apply(p_hist, p_len, _exact(flag, u8, (B,), "flag"), B, h, int(head), cells.ctypes.data, m, L,
+                                             None if st is None else st.ctypes.data, S, _dev(weights, i32, E, "weights"),
+                                             _dev(acc, i64, E, "acc"), _dev(abs_acc, i64, E, "abs_acc", optional=True),
+                                             _dev(cnt, i32, E, "cnt"), _dev(coh_e, i32, E, "coh_e", optional=True),
+                                             _dev(coh_a, i32, E, "coh_a", optional=True), _stream()),
+           "g2048_ntuple_delayed_apply")
+
+
+def ntuple_delayed_link(tr_boards_row, tr_meta_row, slot: int, prev_after, flag, hist, hist_len):
+    """``ntuple_link`` for the delayed learner: the new afterstate goes to prev_after u8 [B,16] and to hist[slot], hist_len u8 [B]
+    grows by one up to h and restarts at 1 after an episode end (the old flag == 2)."""
+    B = flag.numel()
+    p_hist, p_len, h = _ring(hist, hist_len, B)
+    _check(load().g2048_ntuple_delayed_link(_dev(tr_boards_row, u8, 16 * B, "tr_boards_row"), _dev(tr_meta_row, u8, B, "tr_meta_row"), B,
+                                            h, int(slot), _exact(prev_after, u8, (B, 16), "prev_after"), _exact(flag, u8, (B,), "flag"),
+                                            p_hist, p_len, _stream()),
+           "g2048_ntuple_delayed_link")
+
+
 def attn_fwd(q_ptr: int, k_ptr: int, v_ptr: int, o, lse, B: int, H: int, Sq: int, strides, scale: float, p_drop: float,
              seed: int, seed_state: int = 0):
     """q/k/v: raw device addresses inside bf16 tensors the caller keeps alive; strides = (q_sb, q_ss, k_sb, k_ss,

@@ -24,6 +24,7 @@ from .q_player import QPlayer
 DEFAULT_TUPLES = ((0, 1, 2, 3, 4, 5), (4, 5, 6, 7, 8, 9), (0, 1, 2, 4, 5, 6), (4, 5, 6, 8, 9, 10))
 MAX_TUPLES, MAX_CELLS, MAX_FRAC_BITS = 8, 6, 20
 MAX_STAGES, MAX_STAGE_TILE = 8, 17
+MAX_HORIZON = 8
 SEARCH_CHUNK = 1 << 16  # roots per two-ply call: 128 workspace floats each
 
 
@@ -94,6 +95,33 @@ def _check_carousel_tiles(carousel_tiles, network):
         return _check_stage_tiles(carousel_tiles)
     except ValueError as e:
         raise ValueError(str(e).replace("stage_tiles", "carousel_tiles")) from None
+
+
+def default_horizon(lam: float) -> int:
+    """The smallest h >= 1 with lam^h <= 0.1, capped at ``MAX_HORIZON``: 1 for lam = 0, 4 for lam = 0.5, 8 from lam = 0.75 up."""
+    h = 1
+    while h < MAX_HORIZON and lam ** h > 0.1:
+        h += 1
+    return h
+
+
+def _check_lambda(lam, horizon):
+    """-> (None, None) (off) or (lam as a float in [0, 1], horizon as an int in 1 .. 8); ``ValueError`` for anything else, also for a
+    horizon without lam."""
+    if lam is None:
+        if horizon is not None:
+            raise ValueError(f"horizon={horizon!r} needs lam: the delayed learner is on only when lam is given")
+        return None, None
+    if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)):
+        raise ValueError(f"lam must be None or a number in [0, 1], got {lam!r}")
+    lam = float(lam)
+    if not (np.isfinite(lam) and 0.0 <= lam <= 1.0):
+        raise ValueError(f"lam must be None or a number in [0, 1], got {lam!r}")
+    if horizon is None:
+        return lam, default_horizon(lam)
+    if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)) or not 1 <= int(horizon) <= MAX_HORIZON:
+        raise ValueError(f"horizon must be None or an integer in 1 .. {MAX_HORIZON}, got {horizon!r}")
+    return lam, int(horizon)
 
 
 def _device(device) -> torch.device:
@@ -297,14 +325,30 @@ class NTupleTrainer:
     fallbacks under 0.  The learner is untouched: an ended episode's last update has target 0, and the first ``link`` after a
     restart takes the afterstate of the move played on the pool board.  The key chain advances as without the carousel.  The
     pools, ``reached``, ``turn`` and ``starts`` are env state: they are not in ``state_dict()`` and start afresh on resume.
+
+    ``lam`` turns delayed TD(lambda) / TC(lambda) on (Jaskowski 2017), for either learner: multi-step credit assignment without
+    eligibility traces.  ``None`` (the default) is off: nothing is allocated and the launches and every bit of a run stay as they
+    are.  With ``lam`` in [0, 1] every env keeps a ring of its last ``horizon`` = h afterstates and of their TD errors (``hist`` u8
+    [h, B, 16], ``hist_err`` f32 [h, B], ``hist_len`` u8 [B]; 1 .. 8, by default the smallest h with lam^h <= 0.1 capped at 8: 1 for
+    lam = 0, 4 for lam = 0.5), and the middle pair and ``link`` become ``delayed_accumulate`` -> ``delayed_apply`` and
+    ``delayed_link``, the same number of launches.  An afterstate is still updated exactly once, h - 1 lock-steps after it was
+    reached, by e_0 + lam e_1 + ... + lam^(h-1) e_(h-1), the errors of the h transitions since (a Horner sum of individually
+    rounded f32 operations; everything after it is the integer arithmetic of the learner), so the atomic volume per lock-step is
+    TD(0)'s and a run stays reproducible bit for bit.  At an episode's end the states still in the ring are flushed with the
+    shorter sums they have.  ``horizon=1`` is the plain learner bit for bit for any ``lam``; ``lam=0`` with h > 1 is TD(0) applied
+    h - 1 steps late.  The ring position is ``lock_steps`` mod h, a global count, so ``train(48)`` equals ``train(20); train(28)``.
+    ``prev_after`` stays valid (promotion and the carousel read it), and both work unchanged on top.  ``horizon`` without ``lam``,
+    values out of range and bools raise ``ValueError`` before a device is touched.  The ring is env state: it is not in
+    ``state_dict()`` (which carries ``lam`` and ``horizon``) and starts afresh on resume.
     """
 
     LEARNERS = ("td0", "tc")
 
     def __init__(self, network: NTupleNetwork, num_envs: int, alpha: float = 0.1, seed: int = 0, rng_mode=None, device=None,
-                 learner: str = "td0", promote_every: int = 64, carousel_tiles=None):
+                 learner: str = "td0", promote_every: int = 64, carousel_tiles=None, lam=None, horizon=None):
         if learner not in self.LEARNERS:
             raise ValueError(f"learner must be one of {self.LEARNERS}, got {learner!r}")
+        self.lam, self.horizon = _check_lambda(lam, horizon)
         if isinstance(promote_every, bool) or not isinstance(promote_every, (int, np.integer)) or promote_every < 0:
             raise ValueError(f"promote_every must be a non-negative integer (0: never promote), got {promote_every!r}")
         if not isinstance(network, NTupleNetwork):
@@ -356,6 +400,19 @@ class NTupleTrainer:
             self.reached = torch.zeros(B, dtype=u8, device=dev)
             self.turn = torch.zeros(B, dtype=nv.KEY_DTYPE, device=dev)  # u32 counts, carried as i32 like the keys
             self.starts = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        self.hist = self.hist_err = self.hist_len = None
+        if self.lam is not None:
+            self.hist = torch.zeros((self.horizon, B, 16), dtype=u8, device=dev)
+            self.hist_err = torch.zeros((self.horizon, B), dtype=f32, device=dev)
+            self.hist_len = torch.zeros(B, dtype=u8, device=dev)
+
+    def _learn_delayed(self, count: int, st) -> None:
+        """The middle pair of lock-step ``count`` with ``lam`` on: the newest afterstate is in ring slot (count - 1) mod h."""
+        net, head = self.network, (count - 1) % self.horizon
+        nv.ntuple_delayed_accumulate(self.hist, self.hist_err, self.hist_len, self.flag, self.targets, head, self.lam, net.weights,
+                                     net.cells, net.frac_bits, self.alpha, self.acc, self.abs_acc, self.cnt, self.td_error, st)
+        nv.ntuple_delayed_apply(self.hist, self.hist_len, self.flag, head, net.cells, net.weights, self.acc, self.abs_acc, self.cnt,
+                                self.coh_e, self.coh_a, st)
 
     def _promote_if_reached(self, count: int) -> None:
         """The promotion check in front of lock-step ``count`` (see the class docstring)."""
@@ -394,7 +451,9 @@ class NTupleTrainer:
             self._promote_if_reached(self.lock_steps + t)
             st = net.active_tiles
             nv.ntuple_scores(self.boards, net.weights, net.cells, net.frac_bits, self.scores, self.targets, st)
-            if self.learner == "tc":
+            if self.lam is not None:
+                self._learn_delayed(self.lock_steps + t, st)
+            elif self.learner == "tc":
                 nv.ntuple_tc_accumulate(self.prev_after, self.flag, self.targets, net.weights, net.cells, net.frac_bits, self.alpha,
                                         self.acc, self.abs_acc, self.cnt, self.td_error, st)
                 nv.ntuple_tc_apply(self.prev_after, self.flag, net.cells, net.weights, self.acc, self.abs_acc, self.cnt, self.coh_e,
@@ -406,7 +465,11 @@ class NTupleTrainer:
             nv.policy_step_autoreset(subs[2 * t], subs[2 * t + 1], self.scores, self.targets, True, False, 0, self.boards, self.masks,
                                      self.ep_len, tr["boards"], tr["meta"], tr["rewards"], tr["logp"], tr["values"], B, 0,
                                      self.rng_mode)
-            nv.ntuple_link(tr["boards"][0], tr["meta"][0], self.prev_after, self.flag)
+            if self.lam is not None:
+                nv.ntuple_delayed_link(tr["boards"][0], tr["meta"][0], (self.lock_steps + t) % self.horizon, self.prev_after, self.flag,
+                                       self.hist, self.hist_len)
+            else:
+                nv.ntuple_link(tr["boards"][0], tr["meta"][0], self.prev_after, self.flag)
             if self.carousel_tiles is not None:
                 nv.ntuple_carousel_record(self.boards, self.masks, self.flag, self._carousel, self.reached, self.pool_boards,
                                           self.pool_masks)
@@ -430,24 +493,30 @@ class NTupleTrainer:
         """The learner's own state (host tensors): ``learner``, ``alpha``, ``lock_steps`` and, for ``"tc"``, ``coh_e`` / ``coh_a``, so
         that a resumed run keeps its rates.  The weights are the network's (``NTupleNetwork.save``); the envs start afresh.  On a
         multi-stage network also ``stages`` and ``promotions``; with the carousel on also ``carousel_tiles`` (the thresholds only:
-        the pools are env state and start afresh on resume)."""
+        the pools are env state and start afresh on resume); with the delayed learner on also ``lam`` and ``horizon`` (the ring is
+        env state too)."""
         out = {"learner": self.learner, "alpha": self.alpha, "lock_steps": self.lock_steps}
         if self.network.stage_tiles is not None:
             out.update(stages=self.network.stages, promotions=list(self.promotions))
         if self.carousel_tiles is not None:
             out.update(carousel_tiles=tuple(self.carousel_tiles))
+        if self.lam is not None:
+            out.update(lam=self.lam, horizon=self.horizon)
         if self.learner == "tc":
             out.update(coh_e=self.coh_e.cpu().clone(), coh_a=self.coh_a.cpu().clone())
         return out
 
     def load_state_dict(self, state: dict) -> None:
-        """``ValueError`` for another learner's state, another stage count's, other carousel thresholds (none counts as other), or
-        tables of another shape or dtype; nothing is changed then."""
+        """``ValueError`` for another learner's state, another stage count's, other carousel thresholds (none counts as other), another
+        ``lam`` / ``horizon`` (none counts as other), or tables of another shape or dtype; nothing is changed then."""
         if state.get("learner") != self.learner:
             raise ValueError(f"the state is of learner {state.get('learner')!r}, the trainer's is {self.learner!r}")
         theirs = state.get("carousel_tiles")
         if (None if theirs is None else tuple(int(k) for k in theirs)) != self.carousel_tiles:
             raise ValueError(f"the state is of carousel thresholds {theirs!r}, the trainer's are {self.carousel_tiles!r}")
+        if (state.get("lam"), state.get("horizon")) != (self.lam, self.horizon):
+            raise ValueError(f"the state is of lam {state.get('lam')!r} and horizon {state.get('horizon')!r}, the trainer's are "
+                             f"{self.lam!r} and {self.horizon!r}")
         if state.get("stages", 1) != self.network.stages:
             raise ValueError(f"the state is of a network of {state.get('stages', 1)} stages, the trainer's has {self.network.stages}")
         tables = {}

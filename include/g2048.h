@@ -575,6 +575,59 @@ int g2048_ntuple_carousel_restart(uint32_t sub0, uint32_t sub1, const uint8_t *f
                                   uint8_t *reached, uint32_t *turn, int64_t *starts, uint8_t *start_stage /*may be NULL*/,
                                   int rng_mode, void *stream);
 
+/* ---- n-tuple delayed TD(lambda) (multi-step credit: an afterstate is updated once, h - 1 lock-steps late, by a lambda-sum) ----
+ * A third form of the learner's middle pair and of link, for TD(0) and TC alike (Jaskowski 2017, "delayed" TD(lambda) / TC(lambda):
+ * no eligibility traces, every state is still updated exactly once).  Per trainer: the horizon h in 1 .. 8, lam in [0, 1] (a
+ * double, used as its f32 value) and B envs.  Env state on top of prev_after and flag, all-zero at the start:
+ *   hist u8[h][B][16], a ring of afterstates;  hist_err f32[h][B], their TD errors;  hist_len u8[B], the states the env holds.
+ * The ring position is GLOBAL, not per env.  At lock-step n (the caller's count of lock-steps so far):
+ *   head = (n - 1) mod h holds the newest afterstate A_{n-1}; the state j steps back (j = 1 .. hist_len) sits in slot
+ *   (head - j + 1) mod h; link writes A_n to slot n mod h.
+ * accumulate, for every env with flag != 0 (flag, target, V, c and the tables as for TD(0) / TC above):
+ *   e = sub_rn(flag == 1 ? target : 0, V(hist[head][b])), TD(0)'s e; stored to td_error[b] and to hist_err[head][b];
+ *   x_1 = hist_err[head][b], x_{j+1} = add_rn(hist_err[(head - j) mod h][b], mul_rn(lam, x_j)) for j + 1 <= hist_len[b]: the
+ *     lambda-sums truncated at the ring, from the newest error back, every operation individually rounded;
+ *   state j is DUE if flag == 2 (the episode ended: every j in 1 .. hist_len is flushed) or, with flag == 1, if j == h (which
+ *     needs hist_len == h);
+ *   every due state: delta_j = (int32) rint(clamp(mul_rn(x_j, c), +-2^30)), and at each of the 8 m entries of the board in slot
+ *     (head - j + 1) mod h: acc += delta_j, cnt += 1, for TC also abs_acc += |delta_j|.  The stage is that of the UPDATED board.
+ * apply takes the same due set from flag, hist_len and head; per due board it is td_apply (or, with the TC tables, tc_apply).  A
+ *   second hit of one entry by the same lane finds the exchanged count 0.
+ * link is g2048_ntuple_link, reads the old flag[b] before it writes the new one, stores the afterstate to prev_after[b] AND to
+ *   hist[slot][b], and sets hist_len[b] = min((old flag == 2 ? 0 : hist_len[b]) + 1, h).
+ * h = 1 is TD(0) / TC bit for bit, whatever lam is.  lam = 0 with h > 1 is TD(0) applied h - 1 steps late.  The last h states of an
+ * episode are flushed at its end with the shorter sums they have.  A hist_len above h is read as h.  acc, abs_acc and cnt are
+ * all-zero between lock-steps; everything after e is integer: the result does not depend on scheduling.
+ * stage_tiles / n_stages as in the staged entry points: (NULL, 1) is the unstaged network. */
+
+/* The accumulate half.  abs_acc null: TD(0)'s tables; non-null: TC's.  td_error f32[B] (may be NULL) = e, 0 where flag == 0.  One
+ * lane per env: 8 m gathers, the lambda-sums, then per due state a 16-byte load and the atomic adds of td_accumulate / tc_accumulate.
+ * G2048_EINVAL, before any device work: a null pointer other than abs_acc and td_error, B outside 1 .. 2^28, h outside 1 .. 8, head
+ * outside 0 .. h - 1, lam outside [0, 1] or not finite, the network, stages, frac_bits and alpha as for
+ * g2048_ntuple_staged_td_accumulate, hist not 16-byte aligned, acc or abs_acc not 8-byte aligned, hist_err, target, weights, cnt or
+ * td_error not 4-byte aligned. */
+int g2048_ntuple_delayed_accumulate(const uint8_t *hist, float *hist_err, const uint8_t *hist_len, const uint8_t *flag,
+                                    const float *target, int64_t B, int h, int head, double lam, const int32_t *weights,
+                                    const uint8_t *tuple_cells /*host*/, int m, int L, const uint8_t *stage_tiles /*host*/,
+                                    int n_stages, int frac_bits, double alpha, int64_t *acc, int64_t *abs_acc /*null: TD*/,
+                                    int32_t *cnt, float *td_error, void *stream);
+
+/* The apply half, in a launch of its own after g2048_ntuple_delayed_accumulate on the same ring, flag and head.  abs_acc, coh_e and
+ * coh_a all null: td_apply per due board; none null: tc_apply.
+ * G2048_EINVAL, before any device work: a null pointer other than those three, some but not all of the three null, B, h, head, the
+ * network and stages as above, hist not 16-byte aligned, acc or abs_acc not 8-byte aligned, weights, cnt, coh_e or coh_a not 4-byte
+ * aligned. */
+int g2048_ntuple_delayed_apply(const uint8_t *hist, const uint8_t *hist_len, const uint8_t *flag, int64_t B, int h, int head,
+                               const uint8_t *tuple_cells /*host*/, int m, int L, const uint8_t *stage_tiles /*host*/, int n_stages,
+                               int32_t *weights, int64_t *acc, int64_t *abs_acc, int32_t *cnt, int32_t *coh_e, int32_t *coh_a,
+                               void *stream);
+
+/* After the env step, in place of g2048_ntuple_link: slot = n mod h for the lock-step n that has just been played.  One lane per env.
+ * G2048_EINVAL, before any device work: a null pointer, B outside 1 .. 2^28, h outside 1 .. 8, slot outside 0 .. h - 1,
+ * tr_boards_row, prev_after or hist not 16-byte aligned. */
+int g2048_ntuple_delayed_link(const uint8_t *tr_boards_row, const uint8_t *tr_meta_row, int64_t B, int h, int slot,
+                              uint8_t *prev_after, uint8_t *flag, uint8_t *hist, uint8_t *hist_len, void *stream);
+
 /* ---- policy network (update): attention for 17-token sequences ------------------------------------- */
 
 /* softmax(q k^T * scale) v with attention dropout, head_dim 32, Sk = 17 keys, Sq = 17 queries (or 1: the CLS row

@@ -26,6 +26,11 @@ in (b).  Without it the output is unchanged.
 ``carousel_tiles=--carousel-tiles`` and one without, each ``--train-steps`` lock-steps into training; the two launches
 carousel_record and carousel_restart on the first one's state, and the whole training lock-step of both, alternating on, off, on,
 off in the same process.
+``--delayed`` measures the delayed TC(lambda) learner instead of all of the above and writes ``profiles/ntuple_delayed_probe.json``
+unless ``--out`` says otherwise: at every ``--boards`` env count two TC trainers of the default network at alpha 1.0, one with
+``lam=--lam`` (0.5: horizon 4) and one without, each ``--train-steps`` lock-steps into training; the three launches
+delayed_accumulate, delayed_apply and delayed_link on the first one's state next to tc_accumulate, tc_apply and link on the second's,
+and the whole training lock-step of both, alternating on, off, on, off in the same process.
 Prints one JSON line.
 """
 import argparse
@@ -188,6 +193,62 @@ def carousel_probe(boards, dev, repeats, train_steps, tiles, chunk=50):
     return out
 
 
+def delayed_probe(boards, dev, repeats, train_steps, lam, chunk=50):
+    out = {"lam": lam, "learner": "tc, alpha 1.0", "train_steps": train_steps, "kernels": [], "training_lock_step": []}
+    for B in boards:
+        on = NTupleTrainer(NTupleNetwork(device=dev), B, alpha=1.0, device=dev, learner="tc", lam=lam)
+        off = NTupleTrainer(NTupleNetwork(device=dev), B, alpha=1.0, device=dev, learner="tc")
+        on.train(train_steps), off.train(train_steps)
+        out["horizon"] = h = on.horizon
+        net, head, slot = on.network, (on.lock_steps - 1) % on.horizon, on.lock_steps % on.horizon
+        w, cells, F, m = net.weights, net.cells, net.frac_bits, net.m
+        saved = [t.clone() for t in (w, on.coh_e, on.coh_a, on.hist, on.hist_err, on.hist_len, on.prev_after, on.flag)]
+
+        def zero():
+            on.acc.zero_(), on.abs_acc.zero_(), on.cnt.zero_()
+
+        def accumulate():
+            nv.ntuple_delayed_accumulate(on.hist, on.hist_err, on.hist_len, on.flag, on.targets, head, lam, w, cells, F, on.alpha, on.acc,
+                                         on.abs_acc, on.cnt, on.td_error)
+
+        def prepare_apply():
+            zero(), accumulate()
+
+        nv.ntuple_scores(on.boards, w, cells, F, on.scores, on.targets)
+        zero(), accumulate()
+        live, ended = int((on.flag != 0).sum().item()), int((on.flag == 2).sum().item())
+        due = int(on.cnt.sum().item()) // (8 * m)
+        res = {"boards": B, "envs_with_predecessor": live, "envs_flushing": ended, "due_states": due,
+               "distinct_entries_hit": int((on.cnt > 0).sum().item()), "max_same_address_atomics": int(on.cnt.max().item()),
+               "per_launch": {"delayed_accumulate": f"{8 * m * live} gathers, {(h - 1) * live} f32 ring reads, {due} board loads, "
+                                                    f"{16 * m * due} 64-bit + {8 * m * due} 32-bit atomic adds",
+                              "delayed_apply": f"{due} board loads, {8 * m * due} atomic exchanges",
+                              "delayed_link": f"{B} boards, 19 B in, 34 B out"}}
+        res["delayed_accumulate"] = timed(accumulate, repeats, setup=zero)
+        res["delayed_apply"] = timed(lambda: nv.ntuple_delayed_apply(on.hist, on.hist_len, on.flag, head, cells, w, on.acc, on.abs_acc, on.cnt,
+                                                                     on.coh_e, on.coh_a), repeats, setup=prepare_apply)
+        tr = on._tr
+        res["delayed_link"] = timed(lambda: nv.ntuple_delayed_link(tr["boards"][0], tr["meta"][0], slot, on.prev_after, on.flag, on.hist,
+                                                                   on.hist_len), repeats)
+        zero()
+        for t, s0 in zip((w, on.coh_e, on.coh_a, on.hist, on.hist_err, on.hist_len, on.prev_after, on.flag), saved):
+            t.copy_(s0)  # the timed launches moved them
+        plain = tc_kernel_state(off, f"lam off, {train_steps} lock-steps into training", repeats)
+        res.update(tc_accumulate=plain["tc_accumulate"], tc_apply=plain["tc_apply"])
+        pa, fl = off.prev_after.clone(), off.flag.clone()
+        res["link"] = timed(lambda: nv.ntuple_link(off._tr["boards"][0], off._tr["meta"][0], pa, fl), repeats)
+        out["kernels"].append(res)
+        print(json.dumps(res), flush=True)
+        for run in (1, 2):
+            for name, trainer in (("on", on), ("off", off)):
+                t = timed(lambda: trainer.train(chunk), repeats)
+                out["training_lock_step"].append({"envs": B, "lam": name, "run": run, "lock_steps_per_call": chunk,
+                                                  **{k.replace("_ms", "_ms_per_lock_step"): round(v / chunk, 4) for k, v in t.items()}})
+                print(json.dumps(out["training_lock_step"][-1]), flush=True)
+        del on, off
+    return out
+
+
 def staged_network(dev, stage_tiles):
     """The default network, unstaged or with ``stage_tiles`` and every stage active from the start (promotion is not what is timed)."""
     net = NTupleNetwork(device=dev, stage_tiles=stage_tiles)
@@ -251,6 +312,8 @@ def main():
     ap.add_argument("--carousel", action="store_true", help="measure carousel shaping only (see above)")
     ap.add_argument("--carousel-tiles", type=int, nargs="+", default=[7, 8, 9, 10], metavar="K",
                     help="the carousel's thresholds for --carousel (low enough that the pools fill within --train-steps)")
+    ap.add_argument("--delayed", action="store_true", help="measure the delayed TC(lambda) learner only (see above)")
+    ap.add_argument("--lam", type=float, default=0.5, help="lambda for --delayed")
     ap.add_argument("--only-kernels", action="store_true", help="(a) and (b) only: no player lock-step, no learning speed")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -265,6 +328,16 @@ def main():
                "carousel": carousel_probe(a.boards, dev, a.repeats, a.train_steps, a.carousel_tiles)}
         print(json.dumps(res))
         out = a.out or os.path.join(HERE, "..", "profiles", "ntuple_carousel_probe.json")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        json.dump(res, open(out, "w"), indent=1)
+        return
+    if a.delayed:
+        res = {"command": "python tools/probe_ntuple.py " + " ".join(sys.argv[1:]), "device": torch.cuda.get_device_name(dev),
+               "network": "4 x 6-tuples (default), frac_bits 12, TC at alpha 1.0", "repeats": a.repeats,
+               "timer": "HIP events around one call, 3 warm-up calls, median [min, max]",
+               "delayed": delayed_probe(a.boards, dev, a.repeats, a.train_steps, a.lam)}
+        print(json.dumps(res))
+        out = a.out or os.path.join(HERE, "..", "profiles", "ntuple_delayed_probe.json")
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         json.dump(res, open(out, "w"), indent=1)
         return
