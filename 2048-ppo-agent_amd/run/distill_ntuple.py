@@ -25,18 +25,20 @@ sys.path.insert(0, os.path.dirname(HERE))
 
 import torch  # noqa: E402
 
-from src.ppo import DistillTrainer, NTupleActionFunction, NTupleNetwork, NTupleTrainer, PPOAgent  # noqa: E402
+from src.ppo import DistillTrainer, NTupleActionFunction, NTupleNetwork, NTupleSearchActionFunction, NTupleTrainer, PPOAgent  # noqa: E402
 from src.runs import evaluate_agent, evaluate_ntuple  # noqa: E402
 
 MODEL = dict(observation_dim=31, action_dim=4, hidden_dim=512, d_model=256, nhead=8, num_layers=4, dim_feedforward=1024,
              dropout=0.1, reduction="cls")  # run/train_to_2048.py's
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--teacher", default=None, help="an NTupleNetwork saved by run/train_ntuple.py --save (default: train one here)")
     ap.add_argument("--teacher-minutes", type=float, default=2.0, help="without --teacher: minutes of TC training at alpha 1.0")
     ap.add_argument("--teacher-plies", type=int, default=0, choices=(0, 1, 2), help="expectimax depth the teacher labels (and is evaluated) at")
+    ap.add_argument("--teacher-depth", type=int, default=0, choices=(0, 1, 2, 3), metavar="D",
+                    help="1 2 3: the teacher labels (and is evaluated) with the frontier search at this depth; excludes --teacher-plies")
     ap.add_argument("--envs", type=int, default=4096, help="parallel boards")
     ap.add_argument("--minutes", type=float, default=3.0, help="distillation budget (wall-clock, evaluation excluded)")
     ap.add_argument("--tau", type=float, default=0.0, help="0: the teacher's move; > 0: softmax(q / tau) over the legal moves")
@@ -50,8 +52,14 @@ def main():
     ap.add_argument("--seed", type=int, default=0, help="seed of the weights, the environments and the minibatch draws")
     ap.add_argument("--out", default=None, help="write the JSON result here")
     ap.add_argument("--save-agent", default=None, help="write the final agent's state_dict here")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    if a.teacher_depth and a.teacher_plies:
+        ap.error("--teacher-depth and a non-zero --teacher-plies are mutually exclusive")
+    return a
 
+
+def main():
+    a = parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     if a.teacher:
@@ -67,13 +75,15 @@ def main():
         teacher_info = dict(trained_minutes=round((time.perf_counter() - t0) / 60, 2), lock_steps=nt.lock_steps, learner="tc", alpha=1.0)
         del nt  # (its accumulators are 2 GB)
         torch.cuda.empty_cache()
-    tev = evaluate_ntuple(net, dev, num_episodes=a.eval_episodes, seed=42, plies=a.teacher_plies)
-    teacher_info.update(plies=a.teacher_plies, mean_max_tile=tev["mean_max_tile"], percent=tev["percent"])
-    print(f"teacher at {a.teacher_plies} plies: mean max tile {tev['mean_max_tile']:.1f}  {tev['percent']}", flush=True)
+    tev = evaluate_ntuple(net, dev, num_episodes=a.eval_episodes, seed=42, plies=a.teacher_plies, depth=a.teacher_depth)
+    teacher_info.update(plies=a.teacher_plies, depth=a.teacher_depth, mean_max_tile=tev["mean_max_tile"], percent=tev["percent"])
+    print(f"teacher at {a.teacher_depth or a.teacher_plies} plies: mean max tile {tev['mean_max_tile']:.1f}  {tev['percent']}", flush=True)
 
     torch.manual_seed(a.seed)
     agent = PPOAgent(**MODEL)
-    tr = DistillTrainer(agent, NTupleActionFunction(net, device=dev, plies=a.teacher_plies), a.envs, max(a.capacity, a.batch, a.envs),
+    teacher = (NTupleSearchActionFunction(net, device=dev, depth=a.teacher_depth) if a.teacher_depth
+               else NTupleActionFunction(net, device=dev, plies=a.teacher_plies))
+    tr = DistillTrainer(agent, teacher, a.envs, max(a.capacity, a.batch, a.envs),
                         batch_size=a.batch, tau=a.tau, beta=a.beta, seed=a.seed, device=dev)
 
     def evaluate(minutes, ce, agreement):

@@ -39,7 +39,7 @@ from src.ppo import NTupleNetwork, NTupleTrainer  # noqa: E402
 from src.runs import evaluate_ntuple  # noqa: E402
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096, help="parallel boards")
     ap.add_argument("--minutes", type=float, default=10.0, help="training budget (wall-clock, evaluation excluded)")
@@ -50,6 +50,8 @@ def main():
     ap.add_argument("--eval-episodes", type=int, default=1000)
     ap.add_argument("--eval-plies", type=int, nargs="+", default=[0], choices=(0, 1, 2),
                     help="expectimax depths to evaluate at: every evaluation point plays the same seeds once per depth")
+    ap.add_argument("--eval-depth", type=int, nargs="+", default=[], choices=(1, 2, 3), metavar="D",
+                    help="frontier-search depths (1 2 3) to evaluate at as well, one strength line per depth")
     ap.add_argument("--stage-tiles", type=int, nargs="+", default=None, metavar="K",
                     help="log2 tile thresholds of a multi-stage network, ascending (11 12 13 14: a stage from 2048, 4096, 8192, 16384)")
     ap.add_argument("--promote-every", type=int, default=64, metavar="N", help="lock-steps between two promotion checks (0: never)")
@@ -62,9 +64,14 @@ def main():
     ap.add_argument("--seed", type=int, default=0, help="seed of the training environments")
     ap.add_argument("--out", default=None, help="write the JSON result here")
     ap.add_argument("--save", default=None, help="save the trained network here")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.carousel and args.carousel_tiles:
         ap.error("--carousel takes the network's thresholds, --carousel-tiles its own: give one of them")
+    return args
+
+
+def main():
+    args = parse_args()
 
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -100,16 +107,17 @@ def main():
                 c = trainer.coherence()
                 coherence = dict(entries=int(c["entries"].item()), mean_rate=round(float(c["mean_rate"].item()), 4))
                 print(f"{trained / 60:.2f} min: {coherence['entries']} entries with a rate, mean rate {coherence['mean_rate']}", flush=True)
-            for plies in args.eval_plies:
-                ev = evaluate_ntuple(net, dev, num_episodes=args.eval_episodes, seed=42, plies=plies)
-                ev.update(plies=plies, train_seconds=round(trained, 2), lock_steps=trainer.lock_steps, episodes_trained=episodes,
+            for key, n in [("plies", p) for p in args.eval_plies] + [("depth", d) for d in args.eval_depth]:
+                t_eval = time.perf_counter()
+                ev = evaluate_ntuple(net, dev, num_episodes=args.eval_episodes, seed=42, **{key: n})
+                ev.update({key: n}, eval_seconds=round(time.perf_counter() - t_eval, 2), train_seconds=round(trained, 2), lock_steps=trainer.lock_steps, episodes_trained=episodes,
                           max_abs_weight=int(net.weights.abs().max().item()), active_stages=net.active_stages)
                 if coherence is not None:
                     ev.update(coherence=coherence)
                 if trainer.starts is not None:
                     ev.update(carousel_starts=trainer.starts.cpu().tolist())
                 result["evaluations"].append(ev)
-                print(f"{trained / 60:.2f} min, {trainer.lock_steps} lock-steps, plies {plies}: mean max tile "
+                print(f"{trained / 60:.2f} min, {trainer.lock_steps} lock-steps, {key} {n}: mean max tile "
                       f"{ev['mean_max_tile']:.1f}, percent {ev['percent']}", flush=True)
     result["lock_steps"] = trainer.lock_steps
     result["lock_steps_per_s"] = round(trainer.lock_steps / trained, 1)

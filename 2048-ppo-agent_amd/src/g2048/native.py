@@ -531,6 +531,32 @@ def ntuple_expectimax(boards, weights, tuple_cells, frac_bits: int, plies: int, 
            "g2048_ntuple_staged_expectimax")
 
 
+def ntuple_search_workspace_bytes(B: int, depth: int) -> int:
+    """The bytes of ``workspace`` that ``ntuple_search`` needs for B roots at ``depth`` (the worst case: no list can overflow)."""
+    n = load().g2048_ntuple_search_workspace_bytes(int(B), int(depth))
+    if n < 0:
+        raise NativeError(f"ntuple_search: no workspace size for B={B}, depth={depth} (depth is 1, 2 or 3, B at most 2^20 / 2^16 / 2^12)")
+    return n
+
+
+def ntuple_search(boards, weights, tuple_cells, frac_bits: int, depth: int, gamma: float, dedup: bool, workspace, scores, values,
+                  counts=None, stage_tiles=None):
+    """scores f32 [B,4] = the ``depth``-ply (1, 2 or 3) expectimax Q over the n-tuple network's greedy value, searched on packed lists
+    of afterstates (``dedup``: the equal afterstates of one root merged), values f32 [B] = the max over the legal moves.  workspace:
+    uint8 [>= ntuple_search_workspace_bytes(B, depth)], its contents do not matter; counts: i32 [3] or None, the entries per level."""
+    cells, m, L = _tuple_cells(tuple_cells)
+    B, depth = values.numel(), int(depth)
+    need = ntuple_search_workspace_bytes(B, depth)
+    st, S = (None, 1) if stage_tiles is None else _stages(stage_tiles)
+    args = (_dev(boards, u8, 16 * B, "boards"), B, _dev(weights, i32, S * m * 16 ** L, "weights"), cells.ctypes.data, m, L)
+    tail = (int(frac_bits), depth, float(gamma), int(bool(dedup)), _dev(workspace, u8, need, "workspace"), workspace.numel(),
+            _dev(scores, f32, 4 * B, "scores"), _dev(values, f32, B, "values"), _dev(counts, i32, 3, "counts", optional=True), _stream())
+    if stage_tiles is None:
+        _check(load().g2048_ntuple_search(*args, *tail), "g2048_ntuple_search")
+    else:
+        _check(load().g2048_ntuple_staged_search(*args, st.ctypes.data, S, *tail), "g2048_ntuple_staged_search")
+
+
 def ntuple_td_accumulate(prev_after, flag, target, weights, tuple_cells, frac_bits: int, alpha: float, acc, cnt, td_error=None,
                          stage_tiles=None):
     """The accumulate half of one TD(0) lock-step: acc i64 [m, 16^L] += delta, cnt i32 [m, 16^L] += 1 at the entries of every env

@@ -3,7 +3,7 @@ from .distill import DistillTrainer
 from .expectimax import ExpectimaxActionFunction
 from .lookahead import LookaheadActionFunction
 from .monte_carlo import MonteCarloActionFunction
-from .ntuple import DEFAULT_TUPLES, NTupleActionFunction, NTupleNetwork, NTupleTrainer
+from .ntuple import DEFAULT_TUPLES, NTupleActionFunction, NTupleNetwork, NTupleSearchActionFunction, NTupleTrainer
 from .ppo_agent import MLPAgent, PPOAgent
 from .ppo_trainer import PPOTrainer
 from .rollout_buffer import RolloutBuffer

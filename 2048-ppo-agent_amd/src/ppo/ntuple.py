@@ -41,6 +41,17 @@ def _check_search(plies, gamma):
     return int(plies), g
 
 
+FRONTIER_CHUNK = {1: 1 << 16, 2: 1 << 13, 3: 1 << 8}  # roots per frontier-search call: about 6 MB, 100 MB and 0.36 GB of workspace
+
+
+def _check_depth(depth, gamma):
+    """-> (depth, gamma) as (int, float); ``ValueError`` for a depth that is a bool, not an integer or outside 1 .. 3, and for a gamma
+    that is negative or not finite."""
+    if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not 1 <= int(depth) <= 3:
+        raise ValueError(f"depth must be 1, 2 or 3, got {depth!r}")
+    return int(depth), _check_search(0, gamma)[1]
+
+
 def _check_tuples(tuples) -> np.ndarray:
     try:
         rows = [tuple(int(c) for c in t) for t in tuples]
@@ -155,6 +166,7 @@ class NTupleNetwork:
         shape = (self.m, 16 ** self.L) if self.stage_tiles is None else (self.stages, self.m, 16 ** self.L)
         self.weights = torch.zeros(shape, dtype=torch.int32, device=self.device)
         self._search_ws = None  # the two-ply workspace, allocated at the first two-ply call
+        self._frontier_ws = None  # the frontier search's workspace, allocated at the first ``search`` call
 
     @property
     def active_stages(self) -> int:
@@ -236,6 +248,34 @@ class NTupleNetwork:
                                  self.active_tiles)
         return q, v
 
+    def search(self, boards: torch.Tensor, depth: int, gamma: float = 1.0, dedup: bool = True, return_counts: bool = False):
+        """boards u8 [B, 16] -> (q f32 [B, 4], v f32 [B]) of ``depth``-ply (1, 2 or 3) expectimax whose leaf is ``scores``' v, searched
+        on packed lists of afterstates (``g2048_ntuple_search``); ``dedup`` merges the equal afterstates of one root at every level,
+        which changes no output bit.  At depth 1 and 2 the outputs equal ``expectimax``'s bit for bit.  ``return_counts`` adds an int64
+        [3] tensor: the entries of the three levels, summed over the chunks.  The roots go in chunks (``FRONTIER_CHUNK``: 256 at depth
+        3) through one cached workspace sized for a chunk's worst case, 0.36 GB at depth 3; nothing is read back."""
+        depth, gamma = _check_depth(depth, gamma)
+        boards = boards.contiguous()
+        B = boards.shape[0]
+        q = torch.empty((B, 4), dtype=torch.float32, device=boards.device)
+        v = torch.empty(B, dtype=torch.float32, device=boards.device)
+        total = torch.zeros(3, dtype=torch.int64, device=boards.device) if return_counts else None
+        step = FRONTIER_CHUNK[depth]
+        if B:
+            need = nv.ntuple_search_workspace_bytes(min(B, step), depth)
+            ws = self._frontier_ws
+            if ws is None or ws.device != boards.device or ws.numel() < need:
+                ws = self._frontier_ws = None  # release the smaller one first
+                ws = self._frontier_ws = torch.empty(nv.ntuple_search_workspace_bytes(step, depth), dtype=torch.uint8, device=boards.device)
+            counts = torch.empty(3, dtype=torch.int32, device=boards.device) if return_counts else None
+            for s in range(0, B, step):
+                e = min(B, s + step)
+                nv.ntuple_search(boards[s:e], self.weights, self.cells, self.frac_bits, depth, gamma, dedup, ws, q[s:e], v[s:e], counts,
+                                 self.active_tiles)
+                if return_counts:
+                    total += counts
+        return (q, v, total) if return_counts else (q, v)
+
     def save(self, path: str) -> None:
         torch.save({"weights": self.weights.cpu(), "tuples": self.tuples, "frac_bits": self.frac_bits,
                     "stage_tiles": self.stage_tiles, "active_stages": self._active}, path)
@@ -280,6 +320,31 @@ class NTupleActionFunction(QPlayer):
     def policy_fn(self, boards: torch.Tensor, masks: torch.Tensor = None):
         """boards u8 [B, 16], masks unused (legality is ``afterstate != board``) -> (q f32 [B, 4], v f32 [B])."""
         return self.network.expectimax(boards, self.plies, self.gamma)
+
+    policy_fn.needs_masks = False
+
+
+class NTupleSearchActionFunction(QPlayer):
+    """``act_fn`` plug-in for ``BatchRunner`` whose "logits" are ``NTupleNetwork.search``'s: ``depth`` plies (1, 2 or 3) of
+    expectimax over the n-tuple network on packed, deduplicated lists of afterstates, discounted by ``gamma`` per ply.  Everything
+    else is ``NTupleActionFunction``'s: the engine takes the masked argmax, the recorded ``log_prob`` is no policy probability.  A
+    depth that is a bool, not an integer or outside 1 .. 3, or a bad gamma, raises ``ValueError`` before a device is touched."""
+
+    compact = True
+
+    def __init__(self, network: NTupleNetwork, device=None, rng_mode=None, *, depth: int = 1, gamma: float = 1.0, dedup: bool = True):
+        if not isinstance(network, NTupleNetwork):
+            raise ValueError(f"network must be an NTupleNetwork, got {type(network).__name__}")
+        self.depth, self.gamma = _check_depth(depth, gamma)
+        self.dedup = bool(dedup)
+        self.network = network
+        self.device = device
+        self.rng_mode = rng_mode
+
+    @torch.no_grad()
+    def policy_fn(self, boards: torch.Tensor, masks: torch.Tensor = None):
+        """boards u8 [B, 16], masks unused (legality is ``afterstate != board``) -> (q f32 [B, 4], v f32 [B])."""
+        return self.network.search(boards, self.depth, self.gamma, self.dedup)
 
     policy_fn.needs_masks = False
 

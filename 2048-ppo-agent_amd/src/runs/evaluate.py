@@ -91,11 +91,18 @@ def evaluate_monte_carlo(device, num_episodes: int = 1000, seed: int = 42, agent
             agent.train(was_training)
 
 
-def evaluate_ntuple(network, device, num_episodes: int = 1000, seed: int = 42, rng_mode=None, plies: int = 0, gamma: float = 1.0) -> Dict:
+def evaluate_ntuple(network, device, num_episodes: int = 1000, seed: int = 42, rng_mode=None, plies: int = 0, gamma: float = 1.0,
+                    depth: int = 0, dedup: bool = True) -> Dict:
     """The same protocol (same seeds, same env and key stream) played by ``NTupleActionFunction(network)``: the legal move with the
     best ``reward + V(afterstate)`` under the n-tuple network, no other network involved; ``plies`` (1 or 2) searches that many
-    plies of expectimax over that value first."""
-    from ..ppo.ntuple import NTupleActionFunction
+    plies of expectimax over that value first.  ``depth`` (1, 2 or 3; 0, the default, is off) plays the frontier search instead
+    (``NTupleSearchActionFunction``, ``dedup`` as there); it excludes a non-zero ``plies``."""
+    from ..ppo.ntuple import NTupleActionFunction, NTupleSearchActionFunction
 
+    if isinstance(depth, bool) or depth != 0:
+        if plies != 0:
+            raise ValueError(f"evaluate_ntuple: depth={depth!r} and plies={plies!r} are mutually exclusive")
+        fn = NTupleSearchActionFunction(network, device=device, rng_mode=rng_mode, depth=depth, gamma=gamma, dedup=dedup)
+        return evaluate_max_tile(fn, num_episodes, seed, rng_mode=rng_mode, device=device)
     fn = NTupleActionFunction(network, device=device, rng_mode=rng_mode, plies=plies, gamma=gamma)
     return evaluate_max_tile(fn, num_episodes, seed, rng_mode=rng_mode, device=device)

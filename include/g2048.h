@@ -541,6 +541,45 @@ int g2048_ntuple_staged_tc_apply(const uint8_t *prev_after, const uint8_t *flag,
                                  int L, const uint8_t *stage_tiles /*host*/, int n_stages, int32_t *weights, int64_t *acc,
                                  int64_t *abs_acc, int32_t *cnt, int32_t *coh_e, int32_t *coh_a, void *stream);
 
+/* ---- n-tuple frontier search (1 .. 3 plies of expectimax over the n-tuple network on packed, deduplicated lists of afterstates) ----
+ * A second path next to g2048_ntuple_expectimax, with the same arithmetic continued one level.  For an afterstate x with n >= 1
+ * empty cells and j >= 1:
+ *   E_j(x)   = acc / (float)n (correctly rounded), acc = sum over the empty cells c of x, ascending, starting from +0, of
+ *              0.9f * V_{j-1}(x + tile 2 at c) + 0.1f * V_{j-1}(x + tile 4 at c)
+ *   V_0(p)   = values of g2048_ntuple_scores
+ *   V_j(p)   = the max over the legal a of (float)r(p,a) + gamma * E_j(after_a(p)), +0 if there is none
+ *   Q_d(s,a) = (float)r(s,a) + gamma * E_d(after_a(s)) where a is legal, +0 where not
+ * Every f32 operation is individually rounded; at depth 1 and 2 scores and values equal g2048_ntuple_expectimax's bit for bit.
+ * The frontier of level j is a list of afterstates: A_1 holds the legal afterstates of the roots, A_{j+1} the afterstates
+ * after_a'(x + tile at c) over the entries x of A_j, their empty cells, both tiles and the legal a'.  Per root, without merging,
+ * |A_1| <= 4, |A_2| <= 480, |A_3| <= 57 600.  With dedup != 0 two entries of one level that descend from the same root and hold the
+ * same 16 bytes are one entry; E_j is a function of the board alone, so merging changes no output bit.  Equality is decided on the
+ * 16 bytes.  Merging is complete while a root's level has at most 8 192 unique entries; past that, entries may be appended unmerged
+ * (same bits, more entries).  Roots are never merged with each other.  The lists, the links between the levels and E_j live in
+ * the caller's workspace, sized for the worst case so that no list can overflow; its contents before the call do not matter.
+ * List space is taken from one device-side counter per level: the order of a list depends on scheduling, no value does. */
+
+/* The bytes of workspace for B roots at `depth`: about 0.1 KB per root at depth 1, 12 KB at depth 2, 1.41 MB at depth 3.  -1 for a
+ * depth outside 1 .. 3, B < 1, or B above 2^20 (depth 1), 2^16 (depth 2), 2^12 (depth 3). */
+int64_t g2048_ntuple_search_workspace_bytes(int64_t B, int depth);
+
+/* scores f32[B][4] = Q_depth(boards[b], a), values f32[B] = V_depth(boards[b]); rows at or past B and workspace bytes at or past
+ * g2048_ntuple_search_workspace_bytes(B, depth) are not touched.  counts i32[3] (device, may be NULL) = |A_1|, |A_2|, |A_3| as
+ * built, 0 for the levels beyond depth.  gamma is rounded to f32 once.
+ * G2048_EINVAL, before any device work: a null pointer other than counts, B or depth for which
+ * g2048_ntuple_search_workspace_bytes returns -1, workspace_bytes below that size, the network or frac_bits as for
+ * g2048_ntuple_values, gamma negative or not finite, boards or workspace not 16-byte aligned, weights, scores, values or counts
+ * not 4-byte aligned. */
+int g2048_ntuple_search(const uint8_t *boards, int64_t B, const int32_t *weights, const uint8_t *tuple_cells /*host*/, int m, int L,
+                        int frac_bits, int depth, double gamma, int dedup, void *workspace, int64_t workspace_bytes, float *scores,
+                        float *values, int32_t *counts, void *stream);
+
+/* The same over a multi-stage network (stage_tiles, n_stages as above): every leaf is looked up in its own stage. */
+int g2048_ntuple_staged_search(const uint8_t *boards, int64_t B, const int32_t *weights, const uint8_t *tuple_cells /*host*/, int m,
+                               int L, const uint8_t *stage_tiles /*host*/, int n_stages, int frac_bits, int depth, double gamma,
+                               int dedup, void *workspace, int64_t workspace_bytes, float *scores, float *values, int32_t *counts,
+                               void *stream);
+
 /* ---- n-tuple carousel (carousel shaping: episode starts from per-stage pools of boards, so every stage is trained) ----
  * For a trainer over B always-live envs, after the auto-reset env step and g2048_ntuple_link of a lock-step.  The carousel has its
  * own thresholds carousel_tiles u8[n_tiles], a HOST pointer whose bytes travel in the kernarg: log2 tile values k_1 < ... < k_n in

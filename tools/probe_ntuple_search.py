@@ -14,6 +14,10 @@ into a random rollout.
       from the same boards with the expansion kernels.
   (c) strength: mean max tile and the share of episodes reaching 2048 over ``--episodes`` episodes of the README protocol at plies
       0, 1, 2 for each of ``--eval-seeds``, on that network and on one trained for ``--train-seconds`` of wall-clock at 4 096 envs.
+``--frontier`` probes the frontier search instead (``NTupleNetwork.search``, writes profiles/ntuple_frontier_probe.json): ms per call
+of ``search`` at depth 1, 2 and 3 with the dedup on and off, of the unchanged fused ``expectimax(plies=1 | 2)`` and of the composed
+two-ply pipeline with dedup, alternating in one process on the same boards, the entries per root of every level, and the strength of
+depth 3 against plies 2 on the two networks of (c).
 Prints one JSON line.  ``--trace-calls N`` times nothing: it makes N calls of every variant at the largest board count, for
 ``rocprofv3 --kernel-trace --stats -d DIR -- python tools/probe_ntuple_search.py --trace-calls 10`` (per-kernel times of both paths).
 """
@@ -165,8 +169,79 @@ def strength(net, dev, episodes, seeds, gamma):
     return out
 
 
+def frontier_probe(net, B, dev, repeats, board_steps, gamma):
+    """``NTupleNetwork.search`` at depth 1, 2, 3 with the dedup on and off against the unchanged fused path and the composed two-ply
+    pipeline with dedup, alternating in one process on the same boards; the entries per root of every level."""
+    boards = play_boards(B, dev, board_steps)
+    fns = {"expectimax_plies1": lambda: net.expectimax(boards, 1, gamma),
+           "expectimax_plies2": lambda: net.expectimax(boards, 2, gamma),
+           "composed_plies2_dedup": lambda: composed_two_plies(net, boards, gamma, True)}
+    for depth in (1, 2, 3):
+        for dedup in (True, False):
+            fns[f"search_depth{depth}_{'dedup' if dedup else 'no_dedup'}"] = lambda depth=depth, dedup=dedup: net.search(boards, depth, gamma, dedup)
+    agree = {"depth1": same_bits(fns["search_depth1_dedup"](), fns["expectimax_plies1"]()),
+             "depth2": same_bits(fns["search_depth2_dedup"](), fns["expectimax_plies2"]()),
+             "depth2_no_dedup": same_bits(fns["search_depth2_no_dedup"](), fns["expectimax_plies2"]()),
+             "depth3_dedup_equals_no_dedup": same_bits(fns["search_depth3_dedup"](), fns["search_depth3_no_dedup"]())}
+    counts = {}
+    for dedup in (True, False):
+        c = net.search(boards, 3, gamma, dedup, return_counts=True)[2].cpu().tolist()
+        counts["dedup" if dedup else "no_dedup"] = [round(x / B, 2) for x in c]
+    return {"boards": B, "board_steps": board_steps, "gamma": gamma, "search_equals_expectimax_bit_for_bit": agree,
+            "entries_per_root": counts, **timed_alternating(fns, repeats)}
+
+
+def frontier_strength(net, dev, episodes, seeds, gamma):
+    """Depth 3 of the frontier search against plies 2 of the fused path: the same episodes, seconds per evaluation."""
+    out = []
+    for key, n in (("plies", 2), ("depth", 3)):
+        per_seed = []
+        for s in seeds:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ev = evaluate_ntuple(net, dev, num_episodes=episodes, seed=s, gamma=gamma, **{key: n})
+            per_seed.append({"seed": s, "mean_max_tile": ev["mean_max_tile"],
+                             "percent_2048": round(sum(v for k, v in ev["percent"].items() if int(k) >= 2048), 1),
+                             "mean_episode_length": ev["mean_episode_length"], "seconds": round(time.perf_counter() - t0, 1)})
+        means = [r["mean_max_tile"] for r in per_seed]
+        out.append({key: n, "episodes": episodes, "per_seed": per_seed, "mean_max_tile": round(statistics.mean(means), 1),
+                    "min": min(means), "max": max(means)})
+        print(json.dumps(out[-1]), flush=True)
+    return out
+
+
+def frontier_main(a, dev):
+    res = {"command": "python tools/probe_ntuple_search.py " + " ".join(sys.argv[1:]), "device": torch.cuda.get_device_name(dev),
+           "network": "4 x 6-tuples (default), frac_bits 12, alpha 0.1", "repeats": a.repeats,
+           "timer": "HIP events around one call, 3 warm-up calls, median [min, max], the variants alternating", "lock_step": [],
+           "strength": []}
+    net = NTupleNetwork(device=dev)
+    trainer = NTupleTrainer(net, 4096, device=dev)
+    trainer.train(a.train_steps)
+    for B in a.player_boards:
+        res["lock_step"].append(frontier_probe(net, B, dev, a.repeats, a.board_steps, a.gamma))
+        print(json.dumps(res["lock_step"][-1]), flush=True)
+    if a.episodes > 0:
+        res["strength"].append({"network": f"{trainer.lock_steps} lock-steps at 4096 envs",
+                                "by_search": frontier_strength(net, dev, a.episodes, a.eval_seeds, a.gamma)})
+        if a.train_seconds > 0:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < a.train_seconds:
+                trainer.train(50)
+                trainer.boards.max().item()
+            res["strength"].append({"network": f"{a.train_seconds:.0f} s more of training at 4096 envs ({trainer.lock_steps} lock-steps in all)",
+                                    "by_search": frontier_strength(net, dev, a.episodes, a.eval_seeds, a.gamma)})
+    print(json.dumps(res))
+    out = a.out or os.path.join(HERE, "..", "profiles", "ntuple_frontier_probe.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)) or ".", exist_ok=True)
+    json.dump(res, open(out, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--frontier", action="store_true", help="probe the frontier search (NTupleNetwork.search) against the fused and the "
+                    "composed paths instead; writes profiles/ntuple_frontier_probe.json unless --out is given")
     ap.add_argument("--player-boards", type=int, nargs="+", default=[100, 1024, 4096])
     ap.add_argument("--train-steps", type=int, default=2000)
     ap.add_argument("--train-seconds", type=float, default=120.0)
@@ -183,6 +258,8 @@ def main():
         raise SystemExit("probe_ntuple_search.py measures on the GPU; none is visible")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
+    if a.frontier:
+        return frontier_main(a, dev)
     res = {"command": "python tools/probe_ntuple_search.py " + " ".join(sys.argv[1:]), "device": torch.cuda.get_device_name(dev),
            "network": "4 x 6-tuples (default), frac_bits 12, alpha 0.1", "repeats": a.repeats,
            "timer": "HIP events around one call, 3 warm-up calls, median [min, max], the variants alternating", "lock_step": [],
