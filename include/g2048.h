@@ -741,8 +741,8 @@ int g2048_linear_add_ln_bwd(const void *dy, int64_t lddy, const void *wt_packed,
 
 /* ---- MLP policy (BASELINE configs[1]): the update as a handful of launches ---------------------------------------------- */
 
-/* trunk_in on packed boards: y[m] = relu(bias + sum over the 16 cells c of wt[31 c + boards[m][c]]) (bf16 [M][512]) - a one-hot input
- * times W^T is a sum of weight columns (reference: the MLP policy has no counterpart in the reference; its input convention is the
+/* trunk_in on packed boards: y[m] = relu(bias + sum over the 16 cells c of wt[31 c + min(boards[m][c], 30)]) (bf16 [M][512]; an
+ * exponent above 30 counts as class 30, in y and in onehot) - a one-hot input times W^T is a sum of weight columns (reference: the MLP policy has no counterpart in the reference; its input convention is the
  * one-hot observation of src/runs/batch_runner.py:130-136).  wt: bf16 [496][512], the TRANSPOSE of the Linear's weight [512][496];
  * bias f32 [512]; onehot (bf16 [M][512], columns 496.. zero; may be NULL): the one-hot matrix itself, which the weight-gradient launch
  * multiplies with. */

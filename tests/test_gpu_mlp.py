@@ -1,6 +1,7 @@
 """The MLP policy's update path (BASELINE.json configs[1]) through csrc/g2048_mlp.hip: every kernel against its PyTorch composition,
 and the whole policy - logits, values and ALL parameter gradients at minibatch 2048 - against an fp32 PyTorch forward / backward of the
-same weights (the reference has no MLP policy; its heads are src/ppo/ppo_agent.py:72-87 of the reference)."""
+same weights (the reference has no MLP policy; its heads are src/ppo/ppo_agent.py:72-87 of the reference).
+Per-element coverage of the four kernels against float64 (bit-exact integer cases, derived bounds, footprints): tests/test_gpu_mlp_f64.py."""
 import copy
 
 import pytest
