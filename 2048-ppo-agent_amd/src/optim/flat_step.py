@@ -17,6 +17,7 @@ from __future__ import annotations
 import torch
 
 from ..g2048 import native as nv
+from .eager_step import loss_scale
 from .lamb import Lamb
 
 
@@ -132,12 +133,10 @@ class _FlatStep:
         ``self.grad`` is not read).  Their step counter still advances with the others (the kernel keeps one count for all
         parameters)."""
         table = self._chunk_table(tuple(sorted(skip)))
-        scale = tracker = None
+        scale, tracker = loss_scale(scaler, self.device), None
         growth, backoff, interval = 2.0, 0.5, 2000
-        if scaler is not None and scaler.is_enabled():
-            if scaler._scale is None:
-                scaler._lazy_init_scale_growth_tracker(self.device)
-            scale, tracker = scaler._scale, scaler._growth_tracker
+        if scale is not None:
+            tracker = scaler._growth_tracker
             growth, backoff, interval = scaler.get_growth_factor(), scaler.get_backoff_factor(), scaler.get_growth_interval()
         # shadows that were current BEFORE this step stay current through it (the kernel rewrites them with the parameters, or
         # leaves both untouched on a skipped step); one that was stale (a parameter changed behind the optimiser's back) stays

@@ -21,6 +21,7 @@ from ..actions import _common as C
 from ..g2048 import native as nv
 from ..g2048.engine import seed_key
 from ..optim import configure_bert_optimizers
+from ..optim.eager_step import eager_step, loss_scale
 from .ntuple import NTupleActionFunction, NTupleNetwork
 from .torch_action_wrapper import TorchActionFunction
 
@@ -221,11 +222,7 @@ class DistillTrainer:
         with_v = self.value_coef > 0.0
         with ctx:
             logits, values = self.agent(batch["obs"], None)
-            scale = None
-            if self.use_amp and self.scaler.is_enabled():  # the kernel applies the loss scale to its gradients
-                if self.scaler._scale is None:
-                    self.scaler._lazy_init_scale_growth_tracker(self.device)
-                scale = self.scaler._scale
+            scale = loss_scale(self.scaler, self.device)  # the kernel applies the loss scale to its gradients
             sums, _ = _FusedDistillLoss.apply(logits, values.reshape(-1) if with_v else None, batch["masks"], batch["q"],
                                               batch["vt"] if with_v else None, self.tau, self.value_coef, self.entropy_coef, scale,
                                               self._running, self._workspace)
@@ -254,18 +251,7 @@ class DistillTrainer:
             nv.distill_gather(idx, ring["boards"], ring["masks"], ring["q"], ring["vt"] if with_v else None,
                               out=self._mb if with_v else dict(self._mb, vt=None))
             sums = self._loss_backward(self._mb)
-            if self.use_amp:
-                self.scaler.unscale_(self.optimizer)
-                torch.nn.utils.clip_grad_norm_(self.agent.parameters(), MAX_GRAD_NORM)
-                self.scaler.step(self.optimizer)
-                self.scaler.update()
-            else:
-                torch.nn.utils.clip_grad_norm_(self.agent.parameters(), MAX_GRAD_NORM)
-                self.optimizer.step()
-            if self.device.type == "cuda":
-                # torch's fused optimisers do not advance autograd's version counters; the bf16 shadows and the rollout
-                # encoder's packed weights are keyed on them (as in PPOTrainer.update_policy)
-                torch.autograd.graph.increment_version(list(self.agent.parameters()))
+            eager_step(self.optimizer, self.scaler, self.agent.parameters(), MAX_GRAD_NORM, self.device)
             self.lr_scheduler.step()
             self.updates += 1
         return sums

@@ -22,6 +22,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 from torch.amp import GradScaler, autocast
 
+from ..optim.eager_step import eager_step, loss_scale
 from ..optim.flat_step import flat_step_for
 from ..optim import configure_bert_optimizers
 from ..runs.batch_runner import BatchRunner
@@ -123,7 +124,7 @@ class _GraphedFwdBwd:
 
     Inputs are copied into static buffers, the graph is replayed, gradients land in static ``.grad`` tensors
     (or in the flat all-reduce bucket when it exists); clipping, the optimizer and the LR schedule stay eager.
-    Build it while no autograd graph over the agent's parameters is alive (see ``PPOTrainer._eager_fwd_bwd``).
+    Build it while no autograd graph over the agent's parameters is alive (see ``PPOTrainer._loss_backward``).
     Dropout draws fresh masks on every replay (philox offsets for PyTorch's kernels, ``graph_seed_state`` for ours)."""
 
     def __init__(self, trainer: "PPOTrainer", M: int, sample: dict, capture_allreduce: bool = False):
@@ -136,11 +137,10 @@ class _GraphedFwdBwd:
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            trainer._running_sums()  # (allocated outside the capture)
             trainer._acc_in_kernel = False  # (the warm-up passes must not count in the update's logged sums)
             try:
                 for _ in range(3):  # warm-up off the capture stream (allocator, autocast caches, lazy inits)
-                    self._zero()
+                    trainer._zero_grad()
                     self._fwd_bwd()
             finally:
                 trainer._acc_in_kernel = True
@@ -171,16 +171,13 @@ class _GraphedFwdBwd:
         # parameters that received no gradient inside the capture: a replay leaves zeros in their bucket slices (the captured
         # ``v.zero_()``), and after it every ``p.grad`` points somewhere, so the list cannot be recomputed from ``p.grad``; the
         # optimiser step after a replay takes it from here (torch's AdamW leaves such parameters alone: no decay, no moments)
-        self.no_grad = list(getattr(trainer, "_no_grad", ())) if trainer._flat_grad is not None else []
+        self.no_grad = list(trainer._no_grad) if trainer._flat_grad is not None else []
         # the gradients the replay writes (graph pool) / the tensors the optimizer reads after a replay
         self.grads = [p.grad for p in trainer.agent.parameters()]
         if trainer._flat_grad is not None:
             for p, v in zip(trainer._params, trainer._flat_views):
                 p.grad = v
             self.grads = [p.grad for p in trainer.agent.parameters()]
-
-    def _zero(self):
-        self.tr._zero_grad()
 
     def _fwd_bwd(self):
         st = self.static
@@ -234,7 +231,6 @@ class PPOTrainer:
         # fp32 rollouts (rollout_amp False) of a default-shape PPOAgent through the split-fp16 kernels (fused_policy.FusedPolicyF32);
         # None: G2048_ROLLOUT_FP32_NATIVE decides (TorchActionFunction), default off
         self.fp32_native = fp32_native
-        self._acc_in_kernel, self._acc5 = True, None  # see _running_sums
         self.batch_runner = batch_runner
         self.rollout_buffer = rollout_buffer
         self.gamma, self.lambda_gae, self.clip_epsilon = gamma, lambda_gae, clip_epsilon
@@ -243,6 +239,12 @@ class PPOTrainer:
         self.use_action_mask = use_action_mask
         self.device = torch.device(device)
         self.max_samples_per_epoch, self.shuffle_on_reset = max_samples_per_epoch, shuffle_on_reset
+        # f64 [5]: policy, value, entropy, total loss and KL estimate summed over the minibatches of the current ``update_policy``
+        # call.  ONE buffer for the trainer's lifetime (replayed graphs hold its address; it exists before any capture); the fused
+        # loss kernel adds to it (``_acc_in_kernel``; off during a capture's warm-up), everything else through ``acc5 +=``.
+        self._acc5, self._acc_in_kernel = torch.zeros(5, dtype=torch.float64, device=self.device), True
+        # d(total)/d(sums): picks the total loss out of the fused loss kernel's five means
+        self._sel = torch.tensor([0.0, 0.0, 0.0, 1.0, 0.0], device=self.device)
 
         self.mixed_precision = mixed_precision
         self.use_amp = mixed_precision is not None and self.device.type == "cuda"
@@ -292,6 +294,7 @@ class PPOTrainer:
         self.rank = dist.get_rank() if self.world > 1 else 0
         self._group = dist.group.WORLD if self.world > 1 else None
         self._flat_grad = None
+        self._no_grad = []  # see _collect_grads
         # The one collective per optimiser step.  allreduce_dtype "float32" (default: exact mean of the ranks' f32 gradients) or
         # "bfloat16" (G2048_ALLREDUCE_DTYPE=bf16): the bucket travels as bf16 -- 7.9 MB instead of 15.8 MB per step over xGMI, two
         # cast launches extra; gradients are still loss-scaled there, bf16 has f32's exponent range, so nothing overflows and
@@ -323,6 +326,7 @@ class PPOTrainer:
         # armed only around a forward+backward whose gradients ARE all-reduced afterwards (update_policy's eager minibatch, a capture
         # that includes the collectives): a stray backward (graph warm-up, a test calling _loss_backward) must not start one
         self._early_armed = False
+        self._capturing_allreduce = False  # True while a capture that includes the collectives runs (see _two_buckets_now)
         # clip + optimiser + GradScaler bookkeeping as two (AdamW: g2048_opt_step) or three (LAMB: g2048_lamb_step) launches over
         # flat buffers on the device; anything else (Adam, CPU) takes the PyTorch calls of the reference, and so does everything
         # with G2048_FLAT_OPT=0 (the A/B switch)
@@ -470,7 +474,7 @@ class PPOTrainer:
         if self.world <= 1 or not self._early_n or not self._early_armed:
             return False
         capturing = self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
-        return (not capturing) or bool(getattr(self, "_capturing_allreduce", False))
+        return (not capturing) or self._capturing_allreduce
 
     def _start_early_allreduce(self):
         """SUM over ranks of the first ``_early_n`` elements of the bucket, asynchronously (the process group's own stream /
@@ -628,15 +632,11 @@ class PPOTrainer:
         with ctx:
             if fused:
                 logits, values = self.agent(obs, None)
-                scale = None
-                if self.use_amp and self.scaler.is_enabled():  # the kernel applies the loss scale to its gradients
-                    if self.scaler._scale is None:
-                        self.scaler._lazy_init_scale_growth_tracker(self.device)
-                    scale = self.scaler._scale
+                scale = loss_scale(self.scaler if self.use_amp else None, self.device)  # the kernel applies it to its gradients
                 sums, new_lp = _FusedPPOLoss.apply(logits, values.reshape(-1), actions,
                                                    masks if self.use_action_mask else None, old_lp, adv, ret,
                                                    self.clip_epsilon, self.value_loss_coef, self.entropy_coef, scale,
-                                                   self._running_sums() if self._acc_in_kernel else None)
+                                                   self._acc5 if self._acc_in_kernel else None)
             else:
                 loss, pl, vl, el, new_lp = self._compute_ppo_loss(obs, actions, masks, old_lp, adv, ret)
         if zero:
@@ -649,12 +649,12 @@ class PPOTrainer:
                 early = [id(p) for p in self._early_params] if 0 < self._early_n < self._flat_grad.numel() else None
                 sink = GradSink(self._sink_targets, early=early, on_early=self._on_early_grads if early else None)
             with grad_sink(sink):
-                out.backward(self._loss_selector())
+                out.backward(self._sel)
             if sink is not None and sink.written:  # autograd never saw these: point .grad at what the sink wrote
                 for p, v in zip(self._params, self._flat_views):
                     if id(p) in sink.written:
                         p.grad = v
-            d = sums.detach()  # f32 [5] (the kernel has added them to ``_running_sums()`` already)
+            d = sums.detach()  # f32 [5] (the kernel has added them to ``_acc5`` already)
             return d[:4], d[4:5]
         if self.use_amp:
             self.scaler.scale(loss).backward()
@@ -673,20 +673,6 @@ class PPOTrainer:
         except BaseException:
             self._early_armed, self._early_work = False, None
             raise
-
-    def _running_sums(self) -> torch.Tensor:
-        """f64 [5] on the device: policy, value, entropy, total loss and KL estimate summed over the minibatches of the current
-        ``update_policy`` call.  ONE buffer for the trainer's lifetime (replayed graphs hold its address); the fused loss kernel adds
-        to it, everything else through ``acc5 +=``."""
-        if getattr(self, "_acc5", None) is None or self._acc5.device != self.device:
-            self._acc5 = torch.zeros(5, dtype=torch.float64, device=self.device)
-        return self._acc5
-
-    def _loss_selector(self) -> torch.Tensor:
-        """d(total)/d(sums): picks the total loss out of the fused loss kernel's five means."""
-        if getattr(self, "_sel", None) is None or self._sel.device != self.device:
-            self._sel = torch.tensor([0.0, 0.0, 0.0, 1.0, 0.0], device=self.device)
-        return self._sel
 
     def _unpack_batch(self, batch, packed: bool = False):
         """-> (obs, actions, masks, old_log_probs, advantages, returns).  ``packed`` (the fused loss kernel's layout):
@@ -716,6 +702,19 @@ class PPOTrainer:
         return per_rank
 
     # ------------------------------------------------------------------ update
+    def _optimizer_step(self, graphed: Optional[_GraphedFwdBwd]):
+        """Clip, optimiser, GradScaler bookkeeping and LR schedule of one minibatch whose (all-reduced) gradients are in place;
+        ``graphed``: the graph that produced them, if one did."""
+        if graphed is not None and self._flat_grad is not None:
+            self._no_grad = list(graphed.no_grad)  # (see _GraphedFwdBwd: not recoverable from p.grad after a replay)
+        scaler = self.scaler if self.use_amp else None
+        if self._flat_step is not None:
+            self._flat_step.adopt_shadows(list(Bf16Shadow._live))  # (no-op once they are adopted)
+            self._flat_step.step(self.max_grad_norm, scaler, skip=self._no_grad)
+        else:
+            eager_step(self.optimizer, scaler, self.agent.parameters(), self.max_grad_norm, self.device)
+        self.lr_scheduler.step()
+
     def update_policy(self, batch_size: int = 64, n_epochs: int = 4) -> Dict[str, float]:
         """``n_epochs`` passes of minibatch PPO over the rollout buffer; early stop when mean(old - new log-prob)
         of an epoch exceeds ``target_kl``."""
@@ -736,64 +735,39 @@ class PPOTrainer:
             dist.all_reduce(t, op=dist.ReduceOp.MIN, group=self._group)
             n_per_epoch = int(t.item())
         self.agent.train()
-        acc5 = self._running_sums().zero_()  # sums over all minibatches: policy, value, entropy, total, kl
+        acc5 = self._acc5.zero_()  # sums over all minibatches: policy, value, entropy, total, kl
         kl_before = 0.0
         n_updates = 0
         mean_kl = 0.0
-        packed = self._fused_loss_ok() and batches.packed()
+        fused = self._fused_loss_ok()
+        packed = fused and batches.packed()
         for epoch in range(n_epochs):
             done_batches = 0
             for idx in batches.indices():
                 if done_batches >= n_per_epoch:
                     break
-                full = idx.numel() == batch_size
+                use_graph = self.use_hip_graph and idx.numel() == batch_size
                 if packed:
                     # device-resident packed buffer: one gather launch, straight into the graph's static inputs
                     gkey = (batch_size, "packed")
-                    graphed = self._graphs.get(gkey) if (self.use_hip_graph and full) else None
-                    if graphed is not None:
-                        batches.gather_packed(idx, out=graphed.static)
-                        stats, kl = graphed.replay()
-                    else:
-                        sample = batches.gather_packed(idx)
-                        if self.use_hip_graph and full:
-                            graphed = self._build_graph(gkey, batch_size, sample)
-                        stats, kl = graphed.run(sample) if graphed is not None else self._armed_loss_backward(sample)
+                    graphed = self._graphs.get(gkey) if use_graph else None
+                    sample = batches.gather_packed(idx, out=graphed.static if graphed is not None else None)
                 else:
-                    obs, actions, masks, old_lp, adv, ret = self._unpack_batch(batches.gather(idx),
-                                                                               packed=self._fused_loss_ok())
+                    obs, actions, masks, old_lp, adv, ret = self._unpack_batch(batches.gather(idx), packed=fused)
                     sample = dict(obs=obs, actions=actions, masks=masks, old_lp=old_lp, adv=adv, ret=ret)
-                    graphed = None
-                    if self.use_hip_graph and full:
-                        gkey = (batch_size, obs.dtype, tuple(obs.shape[1:]))
-                        graphed = self._graphs.get(gkey) or self._build_graph(gkey, batch_size, sample)
-                    stats, kl = graphed.run(sample) if graphed is not None else self._armed_loss_backward(sample)
+                    gkey = (batch_size, obs.dtype, tuple(obs.shape[1:]))
+                    graphed = self._graphs.get(gkey) if use_graph else None
+                if graphed is None and use_graph:
+                    graphed = self._build_graph(gkey, batch_size, sample)
+                if graphed is None:
+                    stats, kl = self._armed_loss_backward(sample)
+                else:  # (gathered into the static inputs already: nothing to copy)
+                    stats, kl = graphed.replay() if sample is graphed.static else graphed.run(sample)
                 self._early_armed = self.world > 1  # (the collective below may itself split the bucket: CPU / non-sink path)
                 self._allreduce_grads(collective=not (graphed is not None and graphed.allreduce_captured))
                 self._early_armed = False
-                if graphed is not None and self._flat_grad is not None:
-                    self._no_grad = list(graphed.no_grad)  # (see _GraphedFwdBwd: not recoverable from p.grad after a replay)
-                if self._flat_step is not None:
-                    self._flat_step.adopt_shadows(list(Bf16Shadow._live))  # (no-op once they are adopted)
-                    self._flat_step.step(self.max_grad_norm, self.scaler if self.use_amp else None,
-                                         skip=getattr(self, "_no_grad", ()))
-                elif self.use_amp:
-                    self.scaler.unscale_(self.optimizer)
-                    torch.nn.utils.clip_grad_norm_(self.agent.parameters(), self.max_grad_norm)
-                    self.scaler.step(self.optimizer)
-                    self.scaler.update()
-                else:
-                    torch.nn.utils.clip_grad_norm_(self.agent.parameters(), self.max_grad_norm)
-                    self.optimizer.step()
-                if self._flat_step is None and self.device.type == "cuda":
-                    # torch's fused optimisers update the parameters without advancing autograd's version counters
-                    # (measured: an eager update kept running its forward on the bf16 shadows of the FIRST step); everything
-                    # that caches derived weights keys on them (Bf16Shadow, the fused rollout encoder's packed weights)
-                    torch.autograd.graph.increment_version(list(self.agent.parameters()))
-                self.lr_scheduler.step()
-                if kl._base is not None and kl._base is stats._base and kl._base.numel() == 5:
-                    pass  # the fused loss (views of its one [5] tensor): g2048_ppo_loss has added them to acc5 itself
-                else:
+                self._optimizer_step(graphed)
+                if not fused:  # (the fused loss: _loss_backward handed g2048_ppo_loss acc5, which has added this minibatch itself)
                     acc5[:4] += stats
                     acc5[4:] += kl
                 n_updates += 1

@@ -7,8 +7,8 @@ path; ``tests/test_host_logic.py`` calls it on every CPU run, so a torch upgrade
 
 | interface | used by | for |
 |---|---|---|
-| ``GradScaler._scale``, ``._growth_tracker``, ``._lazy_init_scale_growth_tracker(device)`` | optim/flat_step.py, ppo_trainer.py | the device-resident loss scale read by ``g2048_ppo_loss`` / ``g2048_opt_step`` |
-| ``torch.autograd.graph.increment_version(tensors)`` | optim/flat_step.py, ppo_trainer.py | parameters written through raw pointers / by fused optimisers |
+| ``GradScaler._scale``, ``._growth_tracker``, ``._lazy_init_scale_growth_tracker(device)`` | optim/eager_step.py (``loss_scale``), optim/flat_step.py | the device-resident loss scale read by ``g2048_ppo_loss`` / ``g2048_distill_loss`` / ``g2048_opt_step`` |
+| ``torch.autograd.graph.increment_version(tensors)`` | optim/flat_step.py, optim/eager_step.py | parameters written through raw pointers / by fused optimisers |
 | ``torch._addmm_activation(bias, x, w_t, use_gelu=False)`` | hip_ops._LinearRelu, MLPAgent.forward | bias + ReLU in the GEMM epilogue |
 | ``torch._foreach_copy_(dsts, srcs)`` | hip_ops.Bf16Shadow, ppo_trainer._collect_grads | one multi-tensor copy |
 """
