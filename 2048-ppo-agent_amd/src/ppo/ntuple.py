@@ -276,6 +276,40 @@ class NTupleNetwork:
                     total += counts
         return (q, v, total) if return_counts else (q, v)
 
+    def play_episodes(self, num_episodes: int, seed: int = 42, batch_size: int = 100, rng_mode=None, steps_per_launch: int = 2048,
+                      max_steps: int = 1 << 20):
+        """``num_episodes`` greedy games, each to its end, inside the persistent kernel (``g2048_ntuple_episodes``) ->
+        (final_boards u8 [N, 16], ep_len i32 [N], score i64 [N]) as device tensors.  The games are those of the evaluation protocol:
+        batch j holds games ``j * batch_size ..``, is as large as the games it holds and starts its key chain at
+        ``seed_key(seed + j * batch_size)``, so game g of batch j is env g of ``BatchRunner(seed + j * batch_size,
+        NTupleActionFunction(self)).collect(B_j)``, bit for bit.  All batches play at once; a launch plays ``steps_per_launch`` steps
+        (at most 65 536) and the host reads four bytes back per launch.  ``RuntimeError`` past ``max_steps``; ``ValueError`` for a
+        non-positive episode count, batch size or ``steps_per_launch``, before a device is touched."""
+        for name, x in (("num_episodes", num_episodes), ("batch_size", batch_size), ("steps_per_launch", steps_per_launch)):
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or int(x) <= 0:
+                raise ValueError(f"{name} must be a positive integer, got {x!r}")
+        N, bs, n_steps = int(num_episodes), int(batch_size), min(int(steps_per_launch), 65536)
+        mode = C.resolve_rng_mode(rng_mode)
+        dev = self.weights.device
+        heads = np.stack([seed_key(int(seed) + first) for first in range(0, N, bs)])  # one key per batch ...
+        chain = nv.keys_from_numpy(np.repeat(heads, bs, axis=0)[:N], dev)             # ... expanded to the games
+        boards = torch.empty((N, 16), dtype=torch.uint8, device=dev)
+        masks, done = torch.empty(N, dtype=torch.uint8, device=dev), torch.empty(N, dtype=torch.uint8, device=dev)
+        ep_len = torch.empty(N, dtype=torch.int32, device=dev)
+        score = torch.empty(N, dtype=torch.int64, device=dev)
+        live = torch.zeros(1, dtype=torch.int32, device=dev)
+        t = 0
+        while True:
+            live.zero_()
+            nv.ntuple_episodes(t == 0, n_steps, bs, self.weights, self.cells, self.frac_bits, chain, boards, masks, done, ep_len, score,
+                               mode, live, self.active_tiles)
+            t += n_steps
+            if int(live.item()) == 0:
+                break
+            if t >= max_steps:
+                raise RuntimeError("play_episodes exceeded max_steps")
+        return boards, ep_len, score
+
     def save(self, path: str) -> None:
         torch.save({"weights": self.weights.cpu(), "tuples": self.tuples, "frac_bits": self.frac_bits,
                     "stage_tiles": self.stage_tiles, "active_stages": self._active}, path)

@@ -91,14 +91,37 @@ def evaluate_monte_carlo(device, num_episodes: int = 1000, seed: int = 42, agent
             agent.train(was_training)
 
 
+def _max_tile_summary(tiles: np.ndarray, lengths: np.ndarray) -> Dict:
+    """``evaluate_max_tile``'s dict from the max tile and the length of every episode (for an evaluation that plays no ``BatchRunner``)."""
+    tiles = tiles.astype(np.int64)
+    counts = Counter(tiles.tolist())
+    return {
+        "episodes": int(len(tiles)), "mean_max_tile": float(tiles.mean()),
+        "counts": {int(k): int(v) for k, v in sorted(counts.items())},
+        "percent": {int(k): round(100.0 * v / len(tiles), 1) for k, v in sorted(counts.items())},
+        "mean_episode_length": float(lengths.mean()),
+    }
+
+
 def evaluate_ntuple(network, device, num_episodes: int = 1000, seed: int = 42, rng_mode=None, plies: int = 0, gamma: float = 1.0,
-                    depth: int = 0, dedup: bool = True) -> Dict:
+                    depth: int = 0, dedup: bool = True, fused: bool = False) -> Dict:
     """The same protocol (same seeds, same env and key stream) played by ``NTupleActionFunction(network)``: the legal move with the
     best ``reward + V(afterstate)`` under the n-tuple network, no other network involved; ``plies`` (1 or 2) searches that many
     plies of expectimax over that value first.  ``depth`` (1, 2 or 3; 0, the default, is off) plays the frontier search instead
-    (``NTupleSearchActionFunction``, ``dedup`` as there); it excludes a non-zero ``plies``."""
+    (``NTupleSearchActionFunction``, ``dedup`` as there); it excludes a non-zero ``plies``.  ``fused=True`` plays the greedy
+    evaluation (``plies == 0`` and ``depth == 0`` only, anything else raises ``ValueError``) inside the persistent kernel
+    (``NTupleNetwork.play_episodes``): all batches at once, the same games bit for bit, the same dict plus ``"mean_score"``."""
     from ..ppo.ntuple import NTupleActionFunction, NTupleSearchActionFunction
 
+    if fused:
+        if isinstance(plies, bool) or isinstance(depth, bool) or plies != 0 or depth != 0:
+            raise ValueError(f"evaluate_ntuple: fused=True plays the greedy evaluation only, got plies={plies!r}, depth={depth!r}")
+        if isinstance(num_episodes, bool) or not isinstance(num_episodes, (int, np.integer)) or num_episodes <= 0:
+            raise ValueError(f"evaluate_ntuple: num_episodes must be a positive integer, got {num_episodes!r}")
+        boards, ep_len, score = network.play_episodes(num_episodes, seed, min(100, num_episodes), rng_mode)
+        out = _max_tile_summary(1 << boards.max(dim=1).values.cpu().numpy().astype(np.int64), ep_len.cpu().numpy())
+        out["mean_score"] = float(score.cpu().numpy().mean())
+        return out
     if isinstance(depth, bool) or depth != 0:
         if plies != 0:
             raise ValueError(f"evaluate_ntuple: depth={depth!r} and plies={plies!r} are mutually exclusive")

@@ -667,6 +667,38 @@ int g2048_ntuple_delayed_apply(const uint8_t *hist, const uint8_t *hist_len, con
 int g2048_ntuple_delayed_link(const uint8_t *tr_boards_row, const uint8_t *tr_meta_row, int64_t B, int h, int slot,
                               uint8_t *prev_after, uint8_t *flag, uint8_t *hist, uint8_t *hist_len, void *stream);
 
+/* ---- n-tuple episodes (a whole greedy evaluation of the n-tuple network: every game to its end inside a persistent kernel) ----
+ * An evaluation is N games in batches of bs: game i is env g = i mod bs of batch j = i / bs, whose size is B_total = min(bs, N - j bs)
+ * (the last batch may be short).  Every game carries the head of its batch's key chain, chain u32[N][2]; the caller seeds all
+ * games of batch j with the same key.  A game does what the engine does to env g of a lock-step batch of B_total under
+ * g2048_ntuple_scores and g2048_policy_step(use_mask = 1, sample = 0):
+ *   start: key, sub = split(key) (g2048_chain_keys); board, mask = env.init(split(sub, B_total)[g]); done = 0, ep_len = 0, score = 0
+ *   a step of a game with done == 0: key, act_sub = split(key) (not used: nothing is sampled); key, step_sub = split(key);
+ *     q[a] = scores of g2048_ntuple_scores on the board; l[a] = max(q[a] - (mask >> a & 1 ? 0 : 1e8f), -FLT_MAX) (one rounded
+ *     subtraction), action = the first maximum of l; r = env.step(action) with key split(step_sub, B_total)[g];
+ *     ep_len += 1, score += (int64) r (r is -1 for an illegal move, else the merge score: an exact integer).
+ * The mask is the env's, not the "after != board" of the scores: a network whose legal scores lie below -1e8 plays an illegal
+ * move exactly as the engine then does.  A finished game is frozen: board, mask, ep_len, score and chain keep what they held
+ * after its terminal step.  State: boards u8[N][16], masks u8[N], done u8[N], ep_len i32[N], score i64[N], chain u32[N][2]. */
+
+/* n_steps steps (1 .. 65 536) of every game, one quad of lanes per game, the board resident in registers across them; a wave
+ * leaves early once all of its games are done.  start != 0 seeds the games from chain (the state arrays are output only);
+ * start == 0 continues from the state arrays.  Either way all six arrays hold the games' state afterwards; weights are only
+ * read.  Rows at or past N are not touched.  *live_count (device u32, zeroed by the caller; may be NULL) += games still running
+ * afterwards, one atomic per workgroup that has any.  No host key table, no cross-workgroup communication, nothing read back.
+ * G2048_EINVAL, before any device work: a null pointer other than live_count, N outside 1 .. 2^24, bs outside 1 .. 2^20, n_steps
+ * outside 1 .. 65 536, the network or frac_bits as for g2048_ntuple_values, unknown rng_mode, boards not 16-byte aligned, score not
+ * 8-byte aligned, chain, ep_len, weights or live_count not 4-byte aligned. */
+int g2048_ntuple_episodes(int start, int n_steps, int64_t N, int64_t bs, const int32_t *weights, const uint8_t *tuple_cells /*host*/,
+                          int m, int L, int frac_bits, uint32_t *chain, uint8_t *boards, uint8_t *masks, uint8_t *done,
+                          int32_t *ep_len, int64_t *score, int rng_mode, uint32_t *live_count, void *stream);
+
+/* The same over a multi-stage network (stage_tiles, n_stages as above): every afterstate is looked up in its own stage. */
+int g2048_ntuple_staged_episodes(int start, int n_steps, int64_t N, int64_t bs, const int32_t *weights,
+                                 const uint8_t *tuple_cells /*host*/, int m, int L, const uint8_t *stage_tiles /*host*/, int n_stages,
+                                 int frac_bits, uint32_t *chain, uint8_t *boards, uint8_t *masks, uint8_t *done, int32_t *ep_len,
+                                 int64_t *score, int rng_mode, uint32_t *live_count, void *stream);
+
 /* ---- policy network (update): attention for 17-token sequences ------------------------------------- */
 
 /* softmax(q k^T * scale) v with attention dropout, head_dim 32, Sk = 17 keys, Sq = 17 queries (or 1: the CLS row

@@ -31,6 +31,12 @@ unless ``--out`` says otherwise: at every ``--boards`` env count two TC trainers
 ``lam=--lam`` (0.5: horizon 4) and one without, each ``--train-steps`` lock-steps into training; the three launches
 delayed_accumulate, delayed_apply and delayed_link on the first one's state next to tc_accumulate, tc_apply and link on the second's,
 and the whole training lock-step of both, alternating on, off, on, off in the same process.
+``--episodes`` (the flag alone, without a count) measures the persistent episode kernel instead of all of the above and writes
+``profiles/ntuple_episodes_probe.json`` unless ``--out`` says otherwise: one default network trained by TC at alpha 1.0 on 4 096 envs
+for ``--episode-train-steps`` lock-steps; 1 000 evaluation episodes (seed 42) through ``evaluate_ntuple(fused=False)`` and
+``fused=True``, alternating, three runs each after one warm-up of each, host wall time around a device synchronise, the two dicts
+compared; ``fused=True`` alone at 10 000 and 100 000 episodes; the kernel time per step of one launch in which every game stays live,
+at 1 000 and 100 000 games.
 Prints one JSON line.
 """
 import argparse
@@ -38,6 +44,7 @@ import json
 import os
 import statistics
 import sys
+import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", "2048-ppo-agent_amd"))
@@ -296,6 +303,83 @@ def learning_probe(B, dev, steps, episodes):
             "mean_max_tile": ev["mean_max_tile"], "percent": ev["percent"], "max_abs_weight": int(net.weights.abs().max().item())}
 
 
+def episodes_probe(dev, train_steps, latency_steps, chunk=1000):
+    import numpy as np
+
+    from src.actions._common import resolve_rng_mode
+    from src.g2048.engine import seed_key
+
+    net = NTupleNetwork(device=dev)
+    trainer = NTupleTrainer(net, 4096, alpha=1.0, device=dev, learner="tc")
+    for _ in range(train_steps // chunk):
+        trainer.train(chunk)
+    del trainer
+    torch.cuda.empty_cache()
+    out = {"network": f"4 x 6-tuples (default), frac_bits 12, TC at alpha 1.0, 4096 envs, {train_steps} lock-steps",
+           "steps_per_launch": 2048}
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        return r, time.perf_counter() - t
+
+    def spread(x):
+        return {"median_s": round(statistics.median(x), 4), "min_s": round(min(x), 4), "max_s": round(max(x), 4)}
+
+    paths = {"lock_step": lambda: evaluate_ntuple(net, dev, num_episodes=1000, seed=42), "fused": lambda: evaluate_ntuple(net, dev, num_episodes=1000, seed=42, fused=True)}
+    times, dicts = {k: [] for k in paths}, {}
+    for k, fn in paths.items():
+        dicts[k], _ = wall(fn)  # the warm-up
+    for _ in range(3):
+        for k, fn in paths.items():
+            d, dt = wall(fn)
+            times[k].append(dt)
+            assert d == dicts[k], k
+    common = [k for k in dicts["lock_step"]]
+    out["episodes_1000"] = {"lock_step": spread(times["lock_step"]), "fused": spread(times["fused"]),
+                            "dicts_equal_on_every_common_key": all(dicts["fused"][k] == dicts["lock_step"][k] for k in common),
+                            "result": dicts["fused"]}
+    print(json.dumps(out["episodes_1000"]), flush=True)
+    out["fused_only"] = []
+    for N in (10000, 100000):
+        (boards, ep_len, score), dt = wall(lambda: net.play_episodes(N, 42))
+        tiles = (1 << boards.max(dim=1).values.cpu().numpy().astype(np.int64)).astype(np.float64)
+        ln = ep_len.cpu().numpy()
+        out["fused_only"].append({"episodes": N, "wall_s": round(dt, 4), "launches": int(-(-int(ln.max()) // 2048)),
+                                  "mean_episode_length": float(ln.mean()), "longest_episode": int(ln.max()),
+                                  "mean_max_tile": float(tiles.mean()), "mean_max_tile_standard_error": float(tiles.std(ddof=1) / np.sqrt(N)),
+                                  "mean_score": float(score.cpu().numpy().mean())})
+        print(json.dumps(out["fused_only"][-1]), flush=True)
+    out["per_step"] = []
+    mode = resolve_rng_mode(None)
+    for N in (1000, 100000):
+        heads = np.stack([seed_key(42 + first) for first in range(0, N, 100)])
+        chain0 = nv.keys_from_numpy(np.repeat(heads, 100, axis=0)[:N], dev)
+        boards = torch.empty((N, 16), dtype=torch.uint8, device=dev)
+        masks, done = torch.empty(N, dtype=torch.uint8, device=dev), torch.empty(N, dtype=torch.uint8, device=dev)
+        ep_len, score = torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int64, device=dev)
+        live = torch.zeros(1, dtype=torch.int32, device=dev)
+        chain = chain0.clone()
+        steps = latency_steps
+        while True:  # the longest launch, halving from --episode-latency-steps, that no game ends in
+
+            def launch():
+                nv.ntuple_episodes(True, steps, 100, net.weights, net.cells, net.frac_bits, chain, boards, masks, done, ep_len, score,
+                                   mode, live)
+
+            t = timed(launch, 5, setup=lambda: (chain.copy_(chain0), live.zero_()))
+            if int(live.item()) == N or steps == 1:
+                break
+            steps //= 2
+        out["per_step"].append({"games": N, "n_steps": steps, "games_live_afterwards": int(live.item()),
+                                "launch": t, "us_per_step": round(1000.0 * t["median_ms"] / steps, 3),
+                                "default_launch_ms": round(t["median_ms"] * 2048 / steps, 2)})
+        print(json.dumps(out["per_step"][-1]), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--boards", type=int, nargs="+", default=[4096, 65536])
@@ -303,7 +387,10 @@ def main():
     ap.add_argument("--player-boards", type=int, nargs="+", default=[100, 4096])
     ap.add_argument("--train-steps", type=int, default=2000)
     ap.add_argument("--learn-steps", type=int, default=800)
-    ap.add_argument("--episodes", type=int, default=200)
+    ap.add_argument("--episodes", type=int, nargs="?", default=200, const=-1,
+                    help="with a count: the evaluation episodes of (d); alone: measure the persistent episode kernel only (see above)")
+    ap.add_argument("--episode-train-steps", type=int, default=100000, help="TC lock-steps at 4 096 envs before --episodes measures")
+    ap.add_argument("--episode-latency-steps", type=int, default=256, help="steps of the launch --episodes times per step, halved until no game ends in it")
     ap.add_argument("--board-steps", type=int, default=48)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--tc", action="store_true", help="also time the TC learner's two launches and its training lock-step")
@@ -321,6 +408,16 @@ def main():
         raise SystemExit("probe_ntuple.py measures on the GPU; none is visible")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
+    if a.episodes == -1:
+        res = {"command": "python tools/probe_ntuple.py " + " ".join(sys.argv[1:]), "device": torch.cuda.get_device_name(dev),
+               "timer": "evaluations: host wall time around a device synchronise, one warm-up of each path, then 3 runs each, alternating, "
+                        "median [min, max]; per step: HIP events around one launch, 3 warm-up launches, median of 5 [min, max]",
+               "episodes": episodes_probe(dev, a.episode_train_steps, a.episode_latency_steps)}
+        print(json.dumps(res))
+        out = a.out or os.path.join(HERE, "..", "profiles", "ntuple_episodes_probe.json")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        json.dump(res, open(out, "w"), indent=1)
+        return
     if a.carousel:
         res = {"command": "python tools/probe_ntuple.py " + " ".join(sys.argv[1:]), "device": torch.cuda.get_device_name(dev),
                "network": "4 x 6-tuples (default), frac_bits 12, alpha 0.1", "repeats": a.repeats,
