@@ -23,9 +23,10 @@ stage so far (index 0: fresh boards, fallbacks included).
 ``--lam 0.5`` turns delayed TD(lambda) / TC(lambda) on for either learner (``NTupleTrainer(lam=...)``: an afterstate is updated once,
 ``--horizon`` - 1 lock-steps late, by the lambda-sum of the errors since; the default horizon is the smallest h with lam^h <= 0.1,
 capped at 8).  The result records ``lam`` and ``horizon``.
-``--eval-fused`` plays the greedy evaluation (``--eval-plies 0``) inside the persistent episode kernel (``evaluate_ntuple(fused=True)``:
-the same games bit for bit, all batches at once); the other depths stay on the lock-step path.  Every evaluation records
-``mean_score`` where the path reports it and ``eval_seconds``.
+``--eval-fused`` plays the greedy and the one-ply evaluation (``--eval-plies 0 1``) inside the persistent episode kernels
+(``evaluate_ntuple(fused=True)`` and ``evaluate_ntuple_episodes(plies=1)``: the same games bit for bit, all batches at once); two
+plies and ``--eval-depth`` stay on the lock-step path.  Every evaluation records ``mean_score`` where the path reports it and
+``eval_seconds``.
 """
 import argparse
 import json
@@ -39,7 +40,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 import torch  # noqa: E402
 
 from src.ppo import NTupleNetwork, NTupleTrainer  # noqa: E402
-from src.runs import evaluate_ntuple  # noqa: E402
+from src.runs import evaluate_ntuple, evaluate_ntuple_episodes  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -55,7 +56,7 @@ def parse_args(argv=None):
                     help="expectimax depths to evaluate at: every evaluation point plays the same seeds once per depth")
     ap.add_argument("--eval-depth", type=int, nargs="+", default=[], choices=(1, 2, 3), metavar="D",
                     help="frontier-search depths (1 2 3) to evaluate at as well, one strength line per depth")
-    ap.add_argument("--eval-fused", action="store_true", help="play the greedy evaluation (--eval-plies 0) inside the persistent episode kernel")
+    ap.add_argument("--eval-fused", action="store_true", help="play the greedy and the one-ply evaluation (--eval-plies 0 1) inside the persistent episode kernels")
     ap.add_argument("--stage-tiles", type=int, nargs="+", default=None, metavar="K",
                     help="log2 tile thresholds of a multi-stage network, ascending (11 12 13 14: a stage from 2048, 4096, 8192, 16384)")
     ap.add_argument("--promote-every", type=int, default=64, metavar="N", help="lock-steps between two promotion checks (0: never)")
@@ -113,8 +114,11 @@ def main():
                 print(f"{trained / 60:.2f} min: {coherence['entries']} entries with a rate, mean rate {coherence['mean_rate']}", flush=True)
             for key, n in [("plies", p) for p in args.eval_plies] + [("depth", d) for d in args.eval_depth]:
                 t_eval = time.perf_counter()
-                fused = args.eval_fused and key == "plies" and n == 0
-                ev = evaluate_ntuple(net, dev, num_episodes=args.eval_episodes, seed=42, **({"fused": True} if fused else {key: n}))
+                if args.eval_fused and key == "plies" and n == 1:
+                    ev = evaluate_ntuple_episodes(net, num_episodes=args.eval_episodes, seed=42, plies=1)
+                else:
+                    fused = args.eval_fused and key == "plies" and n == 0
+                    ev = evaluate_ntuple(net, dev, num_episodes=args.eval_episodes, seed=42, **({"fused": True} if fused else {key: n}))
                 ev.update({key: n}, eval_seconds=round(time.perf_counter() - t_eval, 2), train_seconds=round(trained, 2), lock_steps=trainer.lock_steps, episodes_trained=episodes,
                           max_abs_weight=int(net.weights.abs().max().item()), active_stages=net.active_stages)
                 if coherence is not None:

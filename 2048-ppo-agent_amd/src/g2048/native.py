@@ -760,6 +760,23 @@ def ntuple_episodes(start: bool, n_steps: int, bs: int, weights, tuple_cells, fr
         _check(load().g2048_ntuple_staged_episodes(*head, st.ctypes.data, S, *tail), "g2048_ntuple_staged_episodes")
 
 
+def ntuple_search_episodes(start: bool, n_steps: int, bs: int, weights, tuple_cells, frac_bits: int, plies: int, gamma: float, chain,
+                           boards, masks, done, ep_len, score, rng_mode: int, live_count=None, stage_tiles=None):
+    """``ntuple_episodes`` with every move chosen by ``plies`` (1) plies of expectimax at discount ``gamma``, one wavefront per game.
+    The operands and the launch semantics are ``ntuple_episodes``'s."""
+    cells, m, L = _tuple_cells(tuple_cells)
+    N = done.numel()
+    st, S = (None, 1) if stage_tiles is None else _stages(stage_tiles)
+    head = (int(bool(start)), int(n_steps), N, int(bs), _dev(weights, i32, S * m * 16 ** L, "weights"), cells.ctypes.data, m, L)
+    tail = (int(frac_bits), int(plies), float(gamma), _exact(chain, KEY_DTYPE, (N, 2), "chain"), _exact(boards, u8, (N, 16), "boards"),
+            _exact(masks, u8, (N,), "masks"), _exact(done, u8, (N,), "done"), _exact(ep_len, i32, (N,), "ep_len"),
+            _exact(score, i64, (N,), "score"), int(rng_mode), _dev(live_count, i32, 1, "live_count", optional=True), _stream())
+    if stage_tiles is None:
+        _check(load().g2048_ntuple_search_episodes(*head, *tail), "g2048_ntuple_search_episodes")
+    else:
+        _check(load().g2048_ntuple_staged_search_episodes(*head, st.ctypes.data, S, *tail), "g2048_ntuple_staged_search_episodes")
+
+
 def attn_fwd(q_ptr: int, k_ptr: int, v_ptr: int, o, lse, B: int, H: int, Sq: int, strides, scale: float, p_drop: float,
              seed: int, seed_state: int = 0):
     """q/k/v: raw device addresses inside bf16 tensors the caller keeps alive; strides = (q_sb, q_ss, k_sb, k_ss,

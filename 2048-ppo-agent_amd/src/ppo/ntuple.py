@@ -26,6 +26,7 @@ MAX_TUPLES, MAX_CELLS, MAX_FRAC_BITS = 8, 6, 20
 MAX_STAGES, MAX_STAGE_TILE = 8, 17
 MAX_HORIZON = 8
 SEARCH_CHUNK = 1 << 16  # roots per two-ply call: 128 workspace floats each
+SEARCH_EPISODE_STEPS = 256  # steps per launch of the searched episode kernel (play_search_episodes has the reason)
 
 
 def _check_search(plies, gamma):
@@ -285,6 +286,25 @@ class NTupleNetwork:
         NTupleActionFunction(self)).collect(B_j)``, bit for bit.  All batches play at once; a launch plays ``steps_per_launch`` steps
         (at most 65 536) and the host reads four bytes back per launch.  ``RuntimeError`` past ``max_steps``; ``ValueError`` for a
         non-positive episode count, batch size or ``steps_per_launch``, before a device is touched."""
+        return self._episodes(num_episodes, seed, batch_size, rng_mode, steps_per_launch, max_steps, 0, 1.0)
+
+    def play_search_episodes(self, num_episodes: int, seed: int = 42, batch_size: int = 100, rng_mode=None, steps_per_launch=None,
+                             max_steps: int = 1 << 20, *, plies: int = 0, gamma: float = 1.0):
+        """``play_episodes`` with the search depth as an argument: ``plies=0`` is ``play_episodes`` itself (its launches, its default of
+        2 048 steps per launch); ``plies=1`` plays every move by one ply of expectimax at discount ``gamma``
+        (``g2048_ntuple_search_episodes``, one wavefront per game), so game g of batch j is env g of ``BatchRunner(seed + j *
+        batch_size, NTupleActionFunction(self, plies=1, gamma=gamma)).collect(B_j)``, bit for bit.  ``ValueError`` before a device is
+        touched for any other ``plies`` (``True`` and 2 included: two plies stay on the lock-step path) and for a gamma that is
+        negative or not finite.  ``steps_per_launch=None`` takes the depth's default, ``SEARCH_EPISODE_STEPS`` for one ply."""
+        plies, gamma = _check_search(plies, gamma)
+        if plies == 2:
+            raise ValueError("play_search_episodes: plies must be 0 or 1, got 2 (two plies play on the lock-step path)")
+        if steps_per_launch is None:
+            steps_per_launch = SEARCH_EPISODE_STEPS if plies else 2048
+        return self._episodes(num_episodes, seed, batch_size, rng_mode, steps_per_launch, max_steps, plies, gamma)
+
+    def _episodes(self, num_episodes, seed, batch_size, rng_mode, steps_per_launch, max_steps, plies: int, gamma: float):
+        """``play_episodes`` (``plies == 0``) and ``play_search_episodes`` (``plies == 1``): the same checks, state and launch loop."""
         for name, x in (("num_episodes", num_episodes), ("batch_size", batch_size), ("steps_per_launch", steps_per_launch)):
             if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or int(x) <= 0:
                 raise ValueError(f"{name} must be a positive integer, got {x!r}")
@@ -301,8 +321,12 @@ class NTupleNetwork:
         t = 0
         while True:
             live.zero_()
-            nv.ntuple_episodes(t == 0, n_steps, bs, self.weights, self.cells, self.frac_bits, chain, boards, masks, done, ep_len, score,
-                               mode, live, self.active_tiles)
+            if plies:
+                nv.ntuple_search_episodes(t == 0, n_steps, bs, self.weights, self.cells, self.frac_bits, plies, gamma, chain, boards,
+                                          masks, done, ep_len, score, mode, live, self.active_tiles)
+            else:
+                nv.ntuple_episodes(t == 0, n_steps, bs, self.weights, self.cells, self.frac_bits, chain, boards, masks, done, ep_len,
+                                   score, mode, live, self.active_tiles)
             t += n_steps
             if int(live.item()) == 0:
                 break

@@ -129,3 +129,16 @@ def evaluate_ntuple(network, device, num_episodes: int = 1000, seed: int = 42, r
         return evaluate_max_tile(fn, num_episodes, seed, rng_mode=rng_mode, device=device)
     fn = NTupleActionFunction(network, device=device, rng_mode=rng_mode, plies=plies, gamma=gamma)
     return evaluate_max_tile(fn, num_episodes, seed, rng_mode=rng_mode, device=device)
+
+
+def evaluate_ntuple_episodes(network, num_episodes: int = 1000, seed: int = 42, rng_mode=None, plies: int = 0, gamma: float = 1.0) -> Dict:
+    """``evaluate_ntuple(network, network's device, num_episodes, seed, rng_mode, plies, gamma)`` played inside the persistent kernels
+    (``NTupleNetwork.play_search_episodes``): all batches at once, the same games bit for bit, the same dict key for key plus
+    ``"mean_score"``.  ``plies`` is 0 (greedy) or 1 (one ply of expectimax at discount ``gamma``); anything else raises
+    ``ValueError`` before a device is touched, as a non-positive ``num_episodes`` does."""
+    if isinstance(num_episodes, bool) or not isinstance(num_episodes, (int, np.integer)) or num_episodes <= 0:
+        raise ValueError(f"evaluate_ntuple_episodes: num_episodes must be a positive integer, got {num_episodes!r}")
+    boards, ep_len, score = network.play_search_episodes(num_episodes, seed, min(100, num_episodes), rng_mode, plies=plies, gamma=gamma)
+    out = _max_tile_summary(1 << boards.max(dim=1).values.cpu().numpy().astype(np.int64), ep_len.cpu().numpy())
+    out["mean_score"] = float(score.cpu().numpy().mean())
+    return out

@@ -699,6 +699,33 @@ int g2048_ntuple_staged_episodes(int start, int n_steps, int64_t N, int64_t bs, 
                                  int frac_bits, uint32_t *chain, uint8_t *boards, uint8_t *masks, uint8_t *done, int32_t *ep_len,
                                  int64_t *score, int rng_mode, uint32_t *live_count, void *stream);
 
+/* ---- n-tuple searched episodes (a whole one-ply expectimax evaluation of the n-tuple network inside a persistent kernel) ----
+ * Everything of "n-tuple episodes" above holds unchanged: the placement of game i, the seed key per batch, the chain steps per move
+ * (the act sub-key consumed and unused), env.step, the frozen finished game and the six state arrays.  The one difference is the
+ * move choice:
+ *   q[a] = Q_1(board, a) of "n-tuple expectimax" at this gamma; l[a] = max(q[a] - (mask >> a & 1 ? 0 : 1e8f), -FLT_MAX) under the
+ *   game's own mask; action = the first maximum of l.
+ * So game g of batch j is env g of a lock-step batch under g2048_ntuple_expectimax(plies = 1) and g2048_policy_step(use_mask = 1,
+ * sample = 0), bit for bit. */
+
+/* n_steps steps (1 .. 65 536) of every game, one wavefront per game in one-wave workgroups, the game replicated in the wave's
+ * lanes: the existing children of the board (at most 120) are packed into a list, four lanes score a child, four lanes reduce
+ * the four actions.  start, the state arrays, rows at or past N and weights as for g2048_ntuple_episodes; a state written with
+ * start continues under the same entry point cut into any launch sizes.  *live_count (device u32, zeroed by the caller; may be
+ * NULL) += games still running afterwards, one atomic per such game and launch.  gamma is used as the f32 it is.
+ * G2048_EINVAL, before any device work: everything g2048_ntuple_episodes refuses, plies other than 1, gamma negative or not finite. */
+int g2048_ntuple_search_episodes(int start, int n_steps, int64_t N, int64_t bs, const int32_t *weights,
+                                 const uint8_t *tuple_cells /*host*/, int m, int L, int frac_bits, int plies, float gamma,
+                                 uint32_t *chain, uint8_t *boards, uint8_t *masks, uint8_t *done, int32_t *ep_len, int64_t *score,
+                                 int rng_mode, uint32_t *live_count, void *stream);
+
+/* The same over a multi-stage network (stage_tiles, n_stages as above): every leaf's afterstate is looked up in its own stage. */
+int g2048_ntuple_staged_search_episodes(int start, int n_steps, int64_t N, int64_t bs, const int32_t *weights,
+                                        const uint8_t *tuple_cells /*host*/, int m, int L, const uint8_t *stage_tiles /*host*/,
+                                        int n_stages, int frac_bits, int plies, float gamma, uint32_t *chain, uint8_t *boards,
+                                        uint8_t *masks, uint8_t *done, int32_t *ep_len, int64_t *score, int rng_mode,
+                                        uint32_t *live_count, void *stream);
+
 /* ---- policy network (update): attention for 17-token sequences ------------------------------------- */
 
 /* softmax(q k^T * scale) v with attention dropout, head_dim 32, Sk = 17 keys, Sq = 17 queries (or 1: the CLS row

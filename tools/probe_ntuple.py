@@ -37,6 +37,9 @@ for ``--episode-train-steps`` lock-steps; 1 000 evaluation episodes (seed 42) th
 ``fused=True``, alternating, three runs each after one warm-up of each, host wall time around a device synchronise, the two dicts
 compared; ``fused=True`` alone at 10 000 and 100 000 episodes; the kernel time per step of one launch in which every game stays live,
 at 1 000 and 100 000 games.
+``--episodes --episodes-plies 1`` measures the searched episode kernel the same way and writes
+``profiles/ntuple_search_episodes_probe.json``: ``evaluate_ntuple(plies=1)`` against ``evaluate_ntuple_episodes(plies=1)``, the scale
+rows through ``play_search_episodes(plies=1)``, the per-step launch through ``g2048_ntuple_search_episodes``.
 Prints one JSON line.
 """
 import argparse
@@ -54,7 +57,7 @@ import torch  # noqa: E402
 from src.g2048 import native as nv  # noqa: E402
 from src.ppo import (LookaheadActionFunction, NTupleActionFunction, NTupleNetwork, NTupleTrainer, PPOAgent,  # noqa: E402
                      TorchActionFunction)
-from src.runs import BatchRunner, evaluate_ntuple  # noqa: E402
+from src.runs import BatchRunner, evaluate_ntuple, evaluate_ntuple_episodes  # noqa: E402
 
 MODEL = dict(observation_dim=31, action_dim=4, hidden_dim=512, d_model=256, nhead=8, num_layers=4, dim_feedforward=1024,
              dropout=0.1, reduction="cls")
@@ -303,11 +306,14 @@ def learning_probe(B, dev, steps, episodes):
             "mean_max_tile": ev["mean_max_tile"], "percent": ev["percent"], "max_abs_weight": int(net.weights.abs().max().item())}
 
 
-def episodes_probe(dev, train_steps, latency_steps, chunk=1000):
+def episodes_probe(dev, train_steps, latency_steps, plies=0, chunk=1000):
     import numpy as np
 
     from src.actions._common import resolve_rng_mode
     from src.g2048.engine import seed_key
+    from src.ppo.ntuple import SEARCH_EPISODE_STEPS
+
+    per_launch = SEARCH_EPISODE_STEPS if plies else 2048
 
     net = NTupleNetwork(device=dev)
     trainer = NTupleTrainer(net, 4096, alpha=1.0, device=dev, learner="tc")
@@ -316,7 +322,7 @@ def episodes_probe(dev, train_steps, latency_steps, chunk=1000):
     del trainer
     torch.cuda.empty_cache()
     out = {"network": f"4 x 6-tuples (default), frac_bits 12, TC at alpha 1.0, 4096 envs, {train_steps} lock-steps",
-           "steps_per_launch": 2048}
+           "steps_per_launch": per_launch, "plies": plies}
 
     def wall(fn):
         torch.cuda.synchronize()
@@ -328,7 +334,8 @@ def episodes_probe(dev, train_steps, latency_steps, chunk=1000):
     def spread(x):
         return {"median_s": round(statistics.median(x), 4), "min_s": round(min(x), 4), "max_s": round(max(x), 4)}
 
-    paths = {"lock_step": lambda: evaluate_ntuple(net, dev, num_episodes=1000, seed=42), "fused": lambda: evaluate_ntuple(net, dev, num_episodes=1000, seed=42, fused=True)}
+    paths = {"lock_step": lambda: evaluate_ntuple(net, dev, num_episodes=1000, seed=42, plies=plies),
+             "fused": lambda: evaluate_ntuple_episodes(net, num_episodes=1000, seed=42, plies=plies)}
     times, dicts = {k: [] for k in paths}, {}
     for k, fn in paths.items():
         dicts[k], _ = wall(fn)  # the warm-up
@@ -344,10 +351,10 @@ def episodes_probe(dev, train_steps, latency_steps, chunk=1000):
     print(json.dumps(out["episodes_1000"]), flush=True)
     out["fused_only"] = []
     for N in (10000, 100000):
-        (boards, ep_len, score), dt = wall(lambda: net.play_episodes(N, 42))
+        (boards, ep_len, score), dt = wall(lambda: net.play_search_episodes(N, 42, plies=plies))
         tiles = (1 << boards.max(dim=1).values.cpu().numpy().astype(np.int64)).astype(np.float64)
         ln = ep_len.cpu().numpy()
-        out["fused_only"].append({"episodes": N, "wall_s": round(dt, 4), "launches": int(-(-int(ln.max()) // 2048)),
+        out["fused_only"].append({"episodes": N, "wall_s": round(dt, 4), "launches": int(-(-int(ln.max()) // per_launch)),
                                   "mean_episode_length": float(ln.mean()), "longest_episode": int(ln.max()),
                                   "mean_max_tile": float(tiles.mean()), "mean_max_tile_standard_error": float(tiles.std(ddof=1) / np.sqrt(N)),
                                   "mean_score": float(score.cpu().numpy().mean())})
@@ -366,8 +373,12 @@ def episodes_probe(dev, train_steps, latency_steps, chunk=1000):
         while True:  # the longest launch, halving from --episode-latency-steps, that no game ends in
 
             def launch():
-                nv.ntuple_episodes(True, steps, 100, net.weights, net.cells, net.frac_bits, chain, boards, masks, done, ep_len, score,
-                                   mode, live)
+                if plies:
+                    nv.ntuple_search_episodes(True, steps, 100, net.weights, net.cells, net.frac_bits, plies, 1.0, chain, boards, masks, done,
+                                              ep_len, score, mode, live)
+                else:
+                    nv.ntuple_episodes(True, steps, 100, net.weights, net.cells, net.frac_bits, chain, boards, masks, done, ep_len, score,
+                                       mode, live)
 
             t = timed(launch, 5, setup=lambda: (chain.copy_(chain0), live.zero_()))
             if int(live.item()) == N or steps == 1:
@@ -375,7 +386,7 @@ def episodes_probe(dev, train_steps, latency_steps, chunk=1000):
             steps //= 2
         out["per_step"].append({"games": N, "n_steps": steps, "games_live_afterwards": int(live.item()),
                                 "launch": t, "us_per_step": round(1000.0 * t["median_ms"] / steps, 3),
-                                "default_launch_ms": round(t["median_ms"] * 2048 / steps, 2)})
+                                "default_launch_ms": round(t["median_ms"] * per_launch / steps, 2)})
         print(json.dumps(out["per_step"][-1]), flush=True)
     return out
 
@@ -389,6 +400,7 @@ def main():
     ap.add_argument("--learn-steps", type=int, default=800)
     ap.add_argument("--episodes", type=int, nargs="?", default=200, const=-1,
                     help="with a count: the evaluation episodes of (d); alone: measure the persistent episode kernel only (see above)")
+    ap.add_argument("--episodes-plies", type=int, default=0, choices=(0, 1), help="with --episodes alone: 0 the greedy kernel, 1 the searched one")
     ap.add_argument("--episode-train-steps", type=int, default=100000, help="TC lock-steps at 4 096 envs before --episodes measures")
     ap.add_argument("--episode-latency-steps", type=int, default=256, help="steps of the launch --episodes times per step, halved until no game ends in it")
     ap.add_argument("--board-steps", type=int, default=48)
@@ -412,9 +424,9 @@ def main():
         res = {"command": "python tools/probe_ntuple.py " + " ".join(sys.argv[1:]), "device": torch.cuda.get_device_name(dev),
                "timer": "evaluations: host wall time around a device synchronise, one warm-up of each path, then 3 runs each, alternating, "
                         "median [min, max]; per step: HIP events around one launch, 3 warm-up launches, median of 5 [min, max]",
-               "episodes": episodes_probe(dev, a.episode_train_steps, a.episode_latency_steps)}
+               "episodes": episodes_probe(dev, a.episode_train_steps, a.episode_latency_steps, a.episodes_plies)}
         print(json.dumps(res))
-        out = a.out or os.path.join(HERE, "..", "profiles", "ntuple_episodes_probe.json")
+        out = a.out or os.path.join(HERE, "..", "profiles", "ntuple_search_episodes_probe.json" if a.episodes_plies else "ntuple_episodes_probe.json")
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         json.dump(res, open(out, "w"), indent=1)
         return
