@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["g2048.hip", "g2048_policy.hip", "g2048_attention.hip", "g2048_layernorm.hip", "g2048_ppo_loss.hip",
            "g2048_linear.hip", "g2048_optim.hip", "g2048_reduce.hip", "g2048_tail.hip", "g2048_dweight.hip", "g2048_rowgemm.hip", "g2048_mlp.hip",
            "g2048_lookahead.hip", "g2048_f32split.hip", "g2048_symmetry.hip", "g2048_symmetry_ensemble.hip", "g2048_mc.hip", "g2048_ntuple.hip",
-           "g2048_ntuple_search.hip", "g2048_ntuple_frontier.hip", "g2048_ntuple_tc.hip", "g2048_ntuple_carousel.hip", "g2048_ntuple_delayed.hip", "g2048_ntuple_episodes.hip",
+           "g2048_ntuple_search.hip", "g2048_ntuple_frontier.hip", "g2048_ntuple_budget.hip", "g2048_ntuple_tc.hip", "g2048_ntuple_carousel.hip", "g2048_ntuple_delayed.hip", "g2048_ntuple_episodes.hip",
            "g2048_ntuple_search_episodes.hip", "g2048_distill.hip"]
 # every header under csrc/ plus the ABI: a new header cannot be forgotten by the staleness check
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "g2048.h")]

@@ -27,6 +27,8 @@ capped at 8).  The result records ``lam`` and ``horizon``.
 (``evaluate_ntuple(fused=True)`` and ``evaluate_ntuple_episodes(plies=1)``: the same games bit for bit, all batches at once); two
 plies and ``--eval-depth`` stay on the lock-step path.  Every evaluation records ``mean_score`` where the path reports it and
 ``eval_seconds``.
+``--eval-budget K`` adds the budgeted search (``evaluate_ntuple_budget``: every board as deep, up to ``--eval-max-depth``, as its
+levels stay within K distinct afterstates) to every evaluation point, recorded under the key ``"budget"`` with its ``max_depth``.
 """
 import argparse
 import json
@@ -40,7 +42,8 @@ sys.path.insert(0, os.path.dirname(HERE))
 import torch  # noqa: E402
 
 from src.ppo import NTupleNetwork, NTupleTrainer  # noqa: E402
-from src.runs import evaluate_ntuple, evaluate_ntuple_episodes  # noqa: E402
+from src.ppo.ntuple import BUDGET_DEFAULT_DEPTH  # noqa: E402
+from src.runs import evaluate_ntuple, evaluate_ntuple_budget, evaluate_ntuple_episodes  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -56,6 +59,10 @@ def parse_args(argv=None):
                     help="expectimax depths to evaluate at: every evaluation point plays the same seeds once per depth")
     ap.add_argument("--eval-depth", type=int, nargs="+", default=[], choices=(1, 2, 3), metavar="D",
                     help="frontier-search depths (1 2 3) to evaluate at as well, one strength line per depth")
+    ap.add_argument("--eval-budget", type=int, default=None, choices=range(4, 24577), metavar="K",
+                    help="evaluate the budgeted search as well: at most K (4 .. 24576) distinct afterstates per level of a board")
+    ap.add_argument("--eval-max-depth", type=int, default=None, choices=range(1, 7), metavar="D",
+                    help="its depth ceiling, 1 .. 6 (default: the search's own); needs --eval-budget")
     ap.add_argument("--eval-fused", action="store_true", help="play the greedy and the one-ply evaluation (--eval-plies 0 1) inside the persistent episode kernels")
     ap.add_argument("--stage-tiles", type=int, nargs="+", default=None, metavar="K",
                     help="log2 tile thresholds of a multi-stage network, ascending (11 12 13 14: a stage from 2048, 4096, 8192, 16384)")
@@ -70,6 +77,8 @@ def parse_args(argv=None):
     ap.add_argument("--out", default=None, help="write the JSON result here")
     ap.add_argument("--save", default=None, help="save the trained network here")
     args = ap.parse_args(argv)
+    if args.eval_max_depth is not None and args.eval_budget is None:
+        ap.error("--eval-max-depth is the depth ceiling of --eval-budget: give that too")
     if args.carousel and args.carousel_tiles:
         ap.error("--carousel takes the network's thresholds, --carousel-tiles its own: give one of them")
     return args
@@ -112,9 +121,14 @@ def main():
                 c = trainer.coherence()
                 coherence = dict(entries=int(c["entries"].item()), mean_rate=round(float(c["mean_rate"].item()), 4))
                 print(f"{trained / 60:.2f} min: {coherence['entries']} entries with a rate, mean rate {coherence['mean_rate']}", flush=True)
-            for key, n in [("plies", p) for p in args.eval_plies] + [("depth", d) for d in args.eval_depth]:
+            budgeted = [] if args.eval_budget is None else [("budget", args.eval_budget)]
+            for key, n in [("plies", p) for p in args.eval_plies] + [("depth", d) for d in args.eval_depth] + budgeted:
                 t_eval = time.perf_counter()
-                if args.eval_fused and key == "plies" and n == 1:
+                if key == "budget":
+                    depth_kw = {} if args.eval_max_depth is None else {"max_depth": args.eval_max_depth}
+                    ev = evaluate_ntuple_budget(net, dev, num_episodes=args.eval_episodes, seed=42, budget=n, **depth_kw)
+                    ev.update(max_depth=depth_kw.get("max_depth", BUDGET_DEFAULT_DEPTH))
+                elif args.eval_fused and key == "plies" and n == 1:
                     ev = evaluate_ntuple_episodes(net, num_episodes=args.eval_episodes, seed=42, plies=1)
                 else:
                     fused = args.eval_fused and key == "plies" and n == 0

@@ -557,6 +557,35 @@ def ntuple_search(boards, weights, tuple_cells, frac_bits: int, depth: int, gamm
         _check(load().g2048_ntuple_staged_search(*args, st.ctypes.data, S, *tail), "g2048_ntuple_staged_search")
 
 
+def ntuple_budget_search_workspace_bytes(B: int, max_depth: int, budget: int) -> int:
+    """The bytes of ``workspace`` that ``ntuple_budget_search`` needs for B roots: every root owns a region per level."""
+    n = load().g2048_ntuple_budget_search_workspace_bytes(int(B), int(max_depth), int(budget))
+    if n < 0:
+        raise NativeError(f"ntuple_budget_search: no workspace size for B={B}, max_depth={max_depth}, budget={budget} (max_depth is "
+                          f"1 .. 6, budget 4 .. 24576, B at most min(2^20, (2^31 - 1) // (128 * the largest region's entries)))")
+    return n
+
+
+def ntuple_budget_search(boards, weights, tuple_cells, frac_bits: int, max_depth: int, budget: int, gamma: float, workspace, scores,
+                         values, depth_used=None, entries=None, stage_tiles=None):
+    """scores f32 [B,4] = the expectimax Q over the n-tuple network's greedy value, every root searched as deep (1 .. ``max_depth``) as
+    its levels hold at most ``budget`` distinct afterstates; values f32 [B] = the max over the legal moves.  workspace: uint8 [>=
+    ntuple_budget_search_workspace_bytes(B, max_depth, budget)], its contents do not matter; depth_used: u8 [B] or None, the depth of
+    every root; entries: i32 [B, 6] or None, its distinct afterstates per level."""
+    cells, m, L = _tuple_cells(tuple_cells)
+    B, max_depth, budget = values.numel(), int(max_depth), int(budget)
+    need = ntuple_budget_search_workspace_bytes(B, max_depth, budget)
+    st, S = (None, 1) if stage_tiles is None else _stages(stage_tiles)
+    args = (_dev(boards, u8, 16 * B, "boards"), B, _dev(weights, i32, S * m * 16 ** L, "weights"), cells.ctypes.data, m, L)
+    tail = (int(frac_bits), max_depth, budget, float(gamma), _dev(workspace, u8, need, "workspace"), workspace.numel(),
+            _dev(scores, f32, 4 * B, "scores"), _dev(values, f32, B, "values"), _dev(depth_used, u8, B, "depth_used", optional=True),
+            _dev(entries, i32, 6 * B, "entries", optional=True), _stream())
+    if stage_tiles is None:
+        _check(load().g2048_ntuple_budget_search(*args, *tail), "g2048_ntuple_budget_search")
+    else:
+        _check(load().g2048_ntuple_staged_budget_search(*args, st.ctypes.data, S, *tail), "g2048_ntuple_staged_budget_search")
+
+
 def ntuple_td_accumulate(prev_after, flag, target, weights, tuple_cells, frac_bits: int, alpha: float, acc, cnt, td_error=None,
                          stage_tiles=None):
     """The accumulate half of one TD(0) lock-step: acc i64 [m, 16^L] += delta, cnt i32 [m, 16^L] += 1 at the entries of every env

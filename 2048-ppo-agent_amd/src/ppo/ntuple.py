@@ -53,6 +53,35 @@ def _check_depth(depth, gamma):
     return int(depth), _check_search(0, gamma)[1]
 
 
+BUDGET_MAX_DEPTH, BUDGET_MIN, BUDGET_MAX = 6, 4, 24576
+BUDGET_WORKSPACE_BYTES = 4 << 30  # the most workspace ``search_budget`` keeps: a chunk is the roots that fit, at least one
+# what ``search_budget`` searches by default ("N-tuple budgeted search", has the measurements behind them)
+BUDGET_DEFAULT_DEPTH, BUDGET_DEFAULT = 4, 8192
+
+
+def _check_budget(max_depth, budget, gamma):
+    """-> (max_depth, budget, gamma) as (int, int, float); ``ValueError`` for a ``max_depth`` or ``budget`` that is a bool, not an
+    integer or outside 1 .. 6 / 4 .. 24 576, and for a gamma that is negative or not finite."""
+    for name, x, lo, hi in (("max_depth", max_depth, 1, BUDGET_MAX_DEPTH), ("budget", budget, BUDGET_MIN, BUDGET_MAX)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not lo <= int(x) <= hi:
+            raise ValueError(f"{name} must be an integer in {lo} .. {hi}, got {x!r}")
+    return int(max_depth), int(budget), _check_search(0, gamma)[1]
+
+
+def budget_chunk(max_depth: int, budget: int) -> int:
+    """The roots per call of ``search_budget``: the most whose workspace stays at or below ``BUDGET_WORKSPACE_BYTES`` (the size is
+    linear in the roots but for 16-byte rounding), at least 1 and at most the entry point's own limit."""
+    size = nv.load().g2048_ntuple_budget_search_workspace_bytes  # -1 past the entry point's limit
+    lo, hi = 1, max(1, BUDGET_WORKSPACE_BYTES // nv.ntuple_budget_search_workspace_bytes(1, max_depth, budget))
+    while lo < hi:  # the largest n that has a size within the bound: both conditions hold up to some n and fail above it
+        mid = (lo + hi + 1) // 2
+        if 0 < size(mid, max_depth, budget) <= BUDGET_WORKSPACE_BYTES:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
 def _check_tuples(tuples) -> np.ndarray:
     try:
         rows = [tuple(int(c) for c in t) for t in tuples]
@@ -168,6 +197,7 @@ class NTupleNetwork:
         self.weights = torch.zeros(shape, dtype=torch.int32, device=self.device)
         self._search_ws = None  # the two-ply workspace, allocated at the first two-ply call
         self._frontier_ws = None  # the frontier search's workspace, allocated at the first ``search`` call
+        self._budget_ws = None  # the budgeted search's workspace, allocated at the first ``search_budget`` call
 
     @property
     def active_stages(self) -> int:
@@ -276,6 +306,34 @@ class NTupleNetwork:
                 if return_counts:
                     total += counts
         return (q, v, total) if return_counts else (q, v)
+
+    def search_budget(self, boards: torch.Tensor, max_depth: int = BUDGET_DEFAULT_DEPTH, budget: int = BUDGET_DEFAULT, gamma: float = 1.0,
+                      return_depths: bool = False):
+        """boards u8 [B, 16] -> (q f32 [B, 4], v f32 [B]) of expectimax whose leaf is ``scores``' v, every root searched as deep as its
+        frontier fits (``g2048_ntuple_budget_search``): to d = the largest depth in 1 .. ``max_depth`` (at most 6) up to which every
+        level of the root holds at most ``budget`` (4 .. 24 576) distinct afterstates.  A root's row equals ``search(root, depth=d)``
+        bit for bit wherever that exists (d <= 3).  ``return_depths`` adds ``depth_used`` u8 [B] = d and ``entries`` i32 [B, 6] = the
+        distinct afterstates of the levels 1 .. d, 0 beyond.  The roots go in chunks (``budget_chunk``) through one cached workspace
+        of at most ``BUDGET_WORKSPACE_BYTES``; nothing is read back."""
+        max_depth, budget, gamma = _check_budget(max_depth, budget, gamma)
+        boards = boards.contiguous()
+        B, dev = boards.shape[0], boards.device
+        q = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        v = torch.empty(B, dtype=torch.float32, device=dev)
+        used = torch.empty(B, dtype=torch.uint8, device=dev) if return_depths else None
+        entries = torch.empty((B, 6), dtype=torch.int32, device=dev) if return_depths else None
+        if B:
+            step = budget_chunk(max_depth, budget)
+            need = nv.ntuple_budget_search_workspace_bytes(min(B, step), max_depth, budget)
+            ws = self._budget_ws
+            if ws is None or ws.device != dev or ws.numel() < need:
+                ws = self._budget_ws = None  # release the smaller one first
+                ws = self._budget_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            for s in range(0, B, step):
+                e = min(B, s + step)
+                nv.ntuple_budget_search(boards[s:e], self.weights, self.cells, self.frac_bits, max_depth, budget, gamma, ws, q[s:e], v[s:e],
+                                        None if used is None else used[s:e], None if entries is None else entries[s:e], self.active_tiles)
+        return (q, v, used, entries) if return_depths else (q, v)
 
     def play_episodes(self, num_episodes: int, seed: int = 42, batch_size: int = 100, rng_mode=None, steps_per_launch: int = 2048,
                       max_steps: int = 1 << 20):
@@ -403,6 +461,32 @@ class NTupleSearchActionFunction(QPlayer):
     def policy_fn(self, boards: torch.Tensor, masks: torch.Tensor = None):
         """boards u8 [B, 16], masks unused (legality is ``afterstate != board``) -> (q f32 [B, 4], v f32 [B])."""
         return self.network.search(boards, self.depth, self.gamma, self.dedup)
+
+    policy_fn.needs_masks = False
+
+
+class NTupleBudgetSearchActionFunction(QPlayer):
+    """``act_fn`` plug-in for ``BatchRunner`` whose "logits" are ``NTupleNetwork.search_budget``'s: expectimax over the n-tuple network
+    on packed, deduplicated lists of afterstates, every board searched as deep (1 .. ``max_depth``) as its levels stay within
+    ``budget`` distinct afterstates, discounted by ``gamma`` per ply.  Everything else is ``NTupleActionFunction``'s: the engine takes
+    the masked argmax, the recorded ``log_prob`` is no policy probability.  A ``max_depth`` or ``budget`` that is a bool, not an
+    integer or out of range (1 .. 6, 4 .. 24 576), or a bad gamma, raises ``ValueError`` before a device is touched."""
+
+    compact = True
+
+    def __init__(self, network: NTupleNetwork, device=None, rng_mode=None, *, max_depth: int = BUDGET_DEFAULT_DEPTH,
+                 budget: int = BUDGET_DEFAULT, gamma: float = 1.0):
+        if not isinstance(network, NTupleNetwork):
+            raise ValueError(f"network must be an NTupleNetwork, got {type(network).__name__}")
+        self.max_depth, self.budget, self.gamma = _check_budget(max_depth, budget, gamma)
+        self.network = network
+        self.device = device
+        self.rng_mode = rng_mode
+
+    @torch.no_grad()
+    def policy_fn(self, boards: torch.Tensor, masks: torch.Tensor = None):
+        """boards u8 [B, 16], masks unused (legality is ``afterstate != board``) -> (q f32 [B, 4], v f32 [B])."""
+        return self.network.search_budget(boards, self.max_depth, self.budget, self.gamma)
 
     policy_fn.needs_masks = False
 

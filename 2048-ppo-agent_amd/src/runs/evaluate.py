@@ -131,6 +131,18 @@ def evaluate_ntuple(network, device, num_episodes: int = 1000, seed: int = 42, r
     return evaluate_max_tile(fn, num_episodes, seed, rng_mode=rng_mode, device=device)
 
 
+def evaluate_ntuple_budget(network, device, num_episodes: int = 1000, seed: int = 42, rng_mode=None, max_depth: int = 4,
+                           budget: int = 8192, gamma: float = 1.0) -> Dict:
+    """The same protocol (same seeds, same env and key stream) played by ``NTupleBudgetSearchActionFunction(network, max_depth=...,
+    budget=..., gamma=...)``: every board searched as deep, up to ``max_depth``, as its levels stay within ``budget`` distinct
+    afterstates (the defaults are ``NTupleNetwork.search_budget``'s).  A bad ``max_depth``, ``budget`` or gamma raises ``ValueError``
+    before a device is touched."""
+    from ..ppo.ntuple import NTupleBudgetSearchActionFunction
+
+    fn = NTupleBudgetSearchActionFunction(network, device=device, rng_mode=rng_mode, max_depth=max_depth, budget=budget, gamma=gamma)
+    return evaluate_max_tile(fn, num_episodes, seed, rng_mode=rng_mode, device=device)
+
+
 def evaluate_ntuple_episodes(network, num_episodes: int = 1000, seed: int = 42, rng_mode=None, plies: int = 0, gamma: float = 1.0) -> Dict:
     """``evaluate_ntuple(network, network's device, num_episodes, seed, rng_mode, plies, gamma)`` played inside the persistent kernels
     (``NTupleNetwork.play_search_episodes``): all batches at once, the same games bit for bit, the same dict key for key plus

@@ -580,6 +580,41 @@ int g2048_ntuple_staged_search(const uint8_t *boards, int64_t B, const int32_t *
                                int dedup, void *workspace, int64_t workspace_bytes, float *scores, float *values, int32_t *counts,
                                void *stream);
 
+/* ---- n-tuple budgeted search (the frontier search, every root as deep as its levels stay within a budget of unique entries) ----
+ * A third path next to g2048_ntuple_expectimax and g2048_ntuple_search.  With A_j, E_j, V_j and Q_d exactly as above, the order of
+ * every f32 operation included, and merging always on:
+ *   U_j(s) = the number of distinct 16-byte afterstates in A_j(s)
+ *   d(s)   = the largest d in 1 .. max_depth with U_j(s) <= budget for every j <= d
+ *   scores(s, a) = Q_{d(s)}(s, a),   values(s) = the max over the legal a, +0 if there is none
+ * U_1 <= 4 <= budget, so d >= 1.  A root without a legal move has U_j = 0 everywhere: it reports d = max_depth and all-zero scores.
+ * U_j is a function of the root's 16 bytes alone, so d(s) and every output bit are the same in every run.  A root's result equals
+ * g2048_ntuple_search at depth d(s) bit for bit wherever that exists (d <= 3), and g2048_ntuple_expectimax at d <= 2.  A level that
+ * would outgrow the budget is abandoned while it is built and never evaluated.  Every root owns a fixed region per level of the
+ * caller's workspace: 4 entries at level 1, 480 at level 2, budget + 512 from level 3 on; its contents before the call do not matter. */
+
+/* The bytes of workspace for B roots.  Per root: 532 bytes per entry of every level's region but the last (list, E, 128 links), 20
+ * per entry of the last; about 5.1 MB at max_depth 4, budget 8 192 and 27.5 MB at max_depth 5, budget 24 576.  -1 for max_depth
+ * outside 1 .. 6, budget outside 4 .. 24 576, B < 1, or B above the per-call limit min(2^20, floor((2^31 - 1) / (128 * the entries
+ * of the largest region))): 668 at budget 24 576 and 1 927 at budget 8 192 from max_depth 3 on, 34 952 at max_depth 2, 2^20 at
+ * max_depth 1.  Within it every element index stays below 2^31 and the workspace below 2^36 bytes. */
+int64_t g2048_ntuple_budget_search_workspace_bytes(int64_t B, int max_depth, int budget);
+
+/* scores f32[B][4], values f32[B] as defined above; depth_used u8[B] (device, may be NULL) = d(s); entries i32[B][6] (device, may be
+ * NULL) = U_j for j <= d(s), 0 beyond.  Rows at or past B and workspace bytes at or past
+ * g2048_ntuple_budget_search_workspace_bytes(B, max_depth, budget) are not touched.  gamma is rounded to f32 once.
+ * G2048_EINVAL, before any device work: everything g2048_ntuple_search refuses (a null pointer other than depth_used and entries,
+ * workspace_bytes below the size, the network, frac_bits, gamma negative or not finite, boards or workspace not 16-byte aligned,
+ * weights, scores, values or entries not 4-byte aligned), and a B, max_depth or budget for which the size function returns -1. */
+int g2048_ntuple_budget_search(const uint8_t *boards, int64_t B, const int32_t *weights, const uint8_t *tuple_cells /*host*/, int m,
+                               int L, int frac_bits, int max_depth, int budget, double gamma, void *workspace, int64_t workspace_bytes,
+                               float *scores, float *values, uint8_t *depth_used, int32_t *entries, void *stream);
+
+/* The same over a multi-stage network (stage_tiles, n_stages as above): every leaf is looked up in its own stage. */
+int g2048_ntuple_staged_budget_search(const uint8_t *boards, int64_t B, const int32_t *weights, const uint8_t *tuple_cells /*host*/,
+                                      int m, int L, const uint8_t *stage_tiles /*host*/, int n_stages, int frac_bits, int max_depth,
+                                      int budget, double gamma, void *workspace, int64_t workspace_bytes, float *scores, float *values,
+                                      uint8_t *depth_used, int32_t *entries, void *stream);
+
 /* ---- n-tuple carousel (carousel shaping: episode starts from per-stage pools of boards, so every stage is trained) ----
  * For a trainer over B always-live envs, after the auto-reset env step and g2048_ntuple_link of a lock-step.  The carousel has its
  * own thresholds carousel_tiles u8[n_tiles], a HOST pointer whose bytes travel in the kernarg: log2 tile values k_1 < ... < k_n in

@@ -18,6 +18,11 @@ into a random rollout.
 of ``search`` at depth 1, 2 and 3 with the dedup on and off, of the unchanged fused ``expectimax(plies=1 | 2)`` and of the composed
 two-ply pipeline with dedup, alternating in one process on the same boards, the entries per root of every level, and the strength of
 depth 3 against plies 2 on the two networks of (c).
+``--budget`` probes the budgeted search (``NTupleNetwork.search_budget``, writes profiles/ntuple_budget_probe.json): ms per call of
+``search(depth=3)`` against ``search_budget(max_depth=5)`` at budgets 1 024 / 8 192 / 24 576 and ``search_budget(max_depth=3)`` at
+the largest budget, alternating in one process, on rollout boards and on boards three quarters into the games the network plays
+itself; the histogram of ``depth_used`` and the leaf-level entries per root; and the strength of depth 3 against budgets 8 192 and
+24 576 at ``max_depth=5`` on the two networks of (c).  The file is rewritten after every finished part.
 Prints one JSON line.  ``--trace-calls N`` times nothing: it makes N calls of every variant at the largest board count, for
 ``rocprofv3 --kernel-trace --stats -d DIR -- python tools/probe_ntuple_search.py --trace-calls 10`` (per-kernel times of both paths).
 """
@@ -37,7 +42,7 @@ from src.g2048 import native as nv  # noqa: E402
 from src.ppo import NTupleActionFunction, NTupleNetwork, NTupleTrainer  # noqa: E402
 from src.ppo.lookahead import expand, expand_level, scan, spawn_children  # noqa: E402
 from src.ppo.q_player import QPlayer  # noqa: E402
-from src.runs import BatchRunner, evaluate_ntuple  # noqa: E402
+from src.runs import BatchRunner, evaluate_ntuple, evaluate_ntuple_budget  # noqa: E402
 
 
 def _stat(ms):
@@ -238,10 +243,107 @@ def frontier_main(a, dev):
     json.dump(res, open(out, "w"), indent=1)
 
 
+def late_boards(net, B, dev):
+    """Board b = the board three quarters into the greedy game env b plays under ``net``."""
+    tr = BatchRunner(init_seed=11, act_fn=NTupleActionFunction(net, device=dev), device=dev).collect(B)
+    t = (tr.ep_len.to(torch.int64) * 3 // 4).clamp(max=tr.T - 1)
+    return tr.boards[t, torch.arange(B, device=dev)].contiguous().clone()
+
+
+BUDGET_VARIANTS = ((5, 1024), (5, 8192), (5, 24576), (3, 24576))  # (max_depth, budget)
+
+
+def budget_probe(net, boards, kind, repeats, gamma):
+    """``search(depth=3)`` against ``search_budget`` at the variants above, alternating in one process on the same boards."""
+    B = boards.shape[0]
+    fns = {"search_depth3": lambda: net.search(boards, 3, gamma)}
+    for D, K in BUDGET_VARIANTS:
+        fns[f"budget{K}_max_depth{D}"] = lambda D=D, K=K: net.search_budget(boards, D, K, gamma)
+    out = {"boards": B, "kind": kind, "gamma": gamma, "variants": {}}
+    want = fns["search_depth3"]()
+    for D, K in BUDGET_VARIANTS:
+        q, v, used, entries = net.search_budget(boards, D, K, gamma, return_depths=True)
+        at3 = used == 3
+        leaf = entries.gather(1, (used.to(torch.int64) - 1)[:, None])[:, 0]
+        out["variants"][f"budget{K}_max_depth{D}"] = {
+            "depth_used_histogram": {d: int((used == d).sum().item()) for d in range(1, D + 1)},
+            "mean_leaf_level_entries_per_root": round(float(leaf.double().mean().item()), 1),
+            "mean_entries_per_root_by_level": [round(x, 1) for x in entries.double().mean(dim=0).cpu().tolist()],
+            "roots_at_depth3_equal_search_depth3_bit_for_bit": bool(torch.equal(q[at3].view(torch.int32), want[0][at3].view(torch.int32)))}
+    out.update(timed_alternating(fns, repeats))
+    return out
+
+
+def budget_strength(net, dev, episodes, seeds, gamma, save, large_seeds=None):
+    """Depth 3 of the frontier search against the budgeted search: the same episodes, seconds per evaluation.  ``large_seeds``: the
+    seeds the largest budget is evaluated at (the others are NOT MEASURED for it)."""
+    out = []
+    for name, kw in (("depth=3", None), ("budget=8192, max_depth=5", dict(max_depth=5, budget=8192)),
+                     ("budget=24576, max_depth=5", dict(max_depth=5, budget=24576))):
+        per_seed = []
+        out.append({"search": name, "episodes": episodes, "per_seed": per_seed})
+        for s in (large_seeds or seeds) if kw and kw["budget"] == 24576 else seeds:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if kw is None:
+                ev = evaluate_ntuple(net, dev, num_episodes=episodes, seed=s, gamma=gamma, depth=3)
+            else:
+                ev = evaluate_ntuple_budget(net, dev, num_episodes=episodes, seed=s, gamma=gamma, **kw)
+            per_seed.append({"seed": s, "mean_max_tile": ev["mean_max_tile"],
+                             "percent_2048": round(sum(v for k, v in ev["percent"].items() if int(k) >= 2048), 1),
+                             "mean_episode_length": ev["mean_episode_length"], "seconds": round(time.perf_counter() - t0, 1)})
+            means = [r["mean_max_tile"] for r in per_seed]
+            out[-1].update(mean_max_tile=round(statistics.mean(means), 1), min=min(means), max=max(means))
+            print(json.dumps({"search": name, **per_seed[-1]}), flush=True)
+            save(out)
+    return out
+
+
+def budget_main(a, dev):
+    res = {"command": "python tools/probe_ntuple_search.py " + " ".join(sys.argv[1:]), "device": torch.cuda.get_device_name(dev),
+           "network": "4 x 6-tuples (default), frac_bits 12, alpha 0.1", "repeats": a.repeats,
+           "timer": "HIP events around one call, 3 warm-up calls, median [min, max], the variants alternating", "lock_step": [],
+           "strength": []}
+    out = a.out or os.path.join(HERE, "..", "profiles", "ntuple_budget_probe.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)) or ".", exist_ok=True)
+
+    def save(partial=None):
+        json.dump(res if partial is None else {**res, "strength_in_progress": partial}, open(out, "w"), indent=1)
+
+    net = NTupleNetwork(device=dev)
+    trainer = NTupleTrainer(net, 4096, device=dev)
+    trainer.train(a.train_steps)
+    for B in a.player_boards:
+        for kind, boards in (("48 lock-steps into a random rollout", play_boards(B, dev, a.board_steps)),
+                             ("three quarters into the network's own greedy games", late_boards(net, B, dev))):
+            res["lock_step"].append(budget_probe(net, boards, kind, a.repeats, a.gamma))
+            print(json.dumps(res["lock_step"][-1]), flush=True)
+            save()
+    if a.episodes > 0:
+        res["strength"].append({"network": f"{trainer.lock_steps} lock-steps at 4096 envs",
+                                "by_search": budget_strength(net, dev, a.episodes, a.eval_seeds, a.gamma, save, a.large_budget_seeds)})
+        save()
+        if a.train_seconds > 0:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < a.train_seconds:
+                trainer.train(50)
+                trainer.boards.max().item()
+            network = f"{a.train_seconds:.0f} s more of training at 4096 envs ({trainer.lock_steps} lock-steps in all)"
+            res["strength"].append({"network": network, "by_search": []})
+            res["strength"][-1]["by_search"] = budget_strength(net, dev, a.episodes, a.eval_seeds, a.gamma, save, a.large_budget_seeds)
+            save()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--budget", action="store_true", help="probe the budgeted search (NTupleNetwork.search_budget) against search(depth=3) "
+                    "instead; writes profiles/ntuple_budget_probe.json unless --out is given")
     ap.add_argument("--frontier", action="store_true", help="probe the frontier search (NTupleNetwork.search) against the fused and the "
                     "composed paths instead; writes profiles/ntuple_frontier_probe.json unless --out is given")
+    ap.add_argument("--large-budget-seeds", type=int, nargs="+", default=None, help="with --budget: evaluate budget 24576 at these seeds only "
+                    "(it costs some twenty times depth 3); default: every one of --eval-seeds")
     ap.add_argument("--player-boards", type=int, nargs="+", default=[100, 1024, 4096])
     ap.add_argument("--train-steps", type=int, default=2000)
     ap.add_argument("--train-seconds", type=float, default=120.0)
@@ -260,6 +362,8 @@ def main():
     torch.cuda.set_device(dev)
     if a.frontier:
         return frontier_main(a, dev)
+    if a.budget:
+        return budget_main(a, dev)
     res = {"command": "python tools/probe_ntuple_search.py " + " ".join(sys.argv[1:]), "device": torch.cuda.get_device_name(dev),
            "network": "4 x 6-tuples (default), frac_bits 12, alpha 0.1", "repeats": a.repeats,
            "timer": "HIP events around one call, 3 warm-up calls, median [min, max], the variants alternating", "lock_step": [],
