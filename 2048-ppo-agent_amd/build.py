@@ -22,8 +22,15 @@ OBJDIR = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "lib", "libg2048.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
 # per-file additions.  g2048_policy.hip: no NaN handling -- without it every fmaxf on an MFMA result gets a
-# canonicalising v_max in front (32 extra vector instructions per attention head in the encoder's softmax)
-EXTRA = {"g2048_policy.hip": ["-fno-honor-nans"]}
+# canonicalising v_max in front (32 extra vector instructions per attention head in the encoder's softmax).
+# -amdgpu-mfma-vgpr-form: the encoder kernels run one wave per SIMD, and for such a function (512 registers) the compiler
+# otherwise selects every MFMA in its AGPR form; each accumulator the vector ALU touches (scores, P.V, the projections awaiting
+# packing, the linear1 chunk pair, bias tiles, the residual's LayerNorm) then costs a v_accvgpr copy per register and touch.
+# With the VGPR form the accumulators live in arch VGPRs; the AGPR half keeps what is parked there on purpose (park_in_agpr: the
+# normalised activations, the masking constants) and takes the allocator's VGPR spills instead of scratch.
+# Static counts and timings: profiles/encoder_vgpr_accumulators.json.
+ENCODER_VGPR_ACC = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
+EXTRA = {"g2048_policy.hip": ["-fno-honor-nans", *ENCODER_VGPR_ACC]}
 
 
 def _stale(target: str, deps) -> bool:
@@ -31,14 +38,29 @@ def _stale(target: str, deps) -> bool:
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    os.makedirs(OBJDIR, exist_ok=True)
+    return _build(OUT, OBJDIR, EXTRA, force, verbose)
+
+
+def build_encoder_agpr_acc(out: str, force: bool = False, verbose: bool = False) -> str:
+    """The A/B arm of profiles/encoder_vgpr_accumulators.json: the same sources with the encoder's previous register placement
+    (every MFMA in its AGPR form: ENCODER_VGPR_ACC left out), as a second library at `out` for G2048_LIB.  Never the product library:
+    build() does not come here."""
+    if os.path.abspath(out) == OUT:
+        raise ValueError("the A/B arm is not built over the product library")
+    extra = dict(EXTRA)
+    extra["g2048_policy.hip"] = [f for f in EXTRA["g2048_policy.hip"] if f not in ENCODER_VGPR_ACC]
+    return _build(os.path.abspath(out), os.path.abspath(out) + ".objs", extra, force, verbose)
+
+
+def _build(out: str, objdir: str, extra: dict, force: bool, verbose: bool) -> str:
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    os.makedirs(objdir, exist_ok=True)
     me = os.path.abspath(__file__)
     jobs = []
     for name in SOURCES:
-        src, obj = os.path.join(CSRC, name), os.path.join(OBJDIR, name.replace(".hip", ".o"))
+        src, obj = os.path.join(CSRC, name), os.path.join(objdir, name.replace(".hip", ".o"))
         if force or _stale(obj, [src, me] + HEADERS):
-            jobs.append(["hipcc", *FLAGS, *EXTRA.get(name, []), "-c", src, "-o", obj])
+            jobs.append(["hipcc", *FLAGS, *extra.get(name, []), "-c", src, "-o", obj])
 
     def run(cmd):
         if verbose:
@@ -48,11 +70,15 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if jobs:
         with ThreadPoolExecutor(max_workers=min(len(jobs), 6)) as pool:
             list(pool.map(run, jobs))
-    objs = [os.path.join(OBJDIR, n.replace(".hip", ".o")) for n in SOURCES]
-    if jobs or _stale(OUT, objs):
-        run(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT, *objs])
-    return OUT
+    objs = [os.path.join(objdir, n.replace(".hip", ".o")) for n in SOURCES]
+    if jobs or _stale(out, objs):
+        run(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, *objs])
+    return out
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose=True))
+    # python build.py [--force] [--encoder-agpr-acc OUT.so]
+    if "--encoder-agpr-acc" in sys.argv:
+        print(build_encoder_agpr_acc(sys.argv[sys.argv.index("--encoder-agpr-acc") + 1], force="--force" in sys.argv, verbose=True))
+    else:
+        print(build(force="--force" in sys.argv, verbose=True))

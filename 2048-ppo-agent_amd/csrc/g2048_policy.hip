@@ -240,6 +240,9 @@ __device__ __forceinline__ void stage_f32(float *dst, const float *src, int n, i
 // Park an MFMA operand fragment in the accumulator half of the register file (MFMA reads A/B operands from either half).
 // With one wave per SIMD the 256 architectural VGPRs are the scarce half: the normalised activations (64 registers) and
 // the masking constants would otherwise crowd out the operand prefetch buffers of the MFMA chains.
+// The accumulators are the other way round: build.py compiles this file with the MFMAs in their VGPR form (-amdgpu-mfma-vgpr-form), so
+// that every accumulator the vector ALU reads or initialises (scores, P.V, q/k/v awaiting packing, the linear1 pair, bias tiles, the
+// residual under LayerNorm) is an arch VGPR from the MFMA that produces it; without the flag each such touch is a v_accvgpr copy.
 __device__ __forceinline__ void park_in_agpr(bf16x8 &x) { asm volatile("" : "+a"(x)); }
 
 // lanes l and l^32 hold the two halves of a token's reduction: one v_permlane32_swap gives both lanes both halves
